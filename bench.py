@@ -13,13 +13,18 @@ k_verify_main).  With N GPUs every rank
 verifies its own 65,536 triples (weak scaling, contiguous index ranges, no
 data-path collective); value = all ranks' verifications / max-over-ranks time.
 
-Also reported:
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up,
+times the K steps, writes the last step's answers (1.0 = accepted) if
+--dump-outputs DIR is given, and prints the result line.  Also in that line:
   roofline      the verify call (k_pre_halve + k_verify_main) against the
                 INT32 VALU issue peak; algorithmic work = the dalek
                 algorithm's field operation count (2,967 mul+sq per verify,
                 frozen by the instrumented C restatement: oracle/coa_oracle.c)
                 x 200 INT32 ops per field op (SURVEY.md 8(d) cost model); its
-                time is measured here with HIP events on the stream it runs on.
+                time is that of the timed steps themselves, measured with HIP
+                events on the stream they run on (no run of its own).
+
+With --full, after the headline's steps (null / "not run" in a plain line):
   cpu_baseline  the C restatement of dalek's algorithms (oracle/, "port")
                 on this host's cores, rank 0 at N=1 only, on a bounded sample.
   secondary     (rank 0, N=1) one C5 shard (2^21 triples) per verify call;
@@ -72,10 +77,17 @@ def parse(argv=None):
                     help="untimed verify calls for this long before the warmup steps, so the timed steps run at "
                          "the GPU's settled clocks (0 = none)")
     ap.add_argument("--n", type=int, default=C2_N, help="triples per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run the CPU baselines and the secondary sections "
+                         "(rank 0, N=1); a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (1.0 per accepted "
+                         "signature, 0.0 per rejected one) to DIR/accepted.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-thread-seconds", type=float, default=24.0,
                     help="CPU work (thread-seconds) of each CPU baseline sample")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3/C4 secondary measurements")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the C3/C4 secondary measurements")
     ap.add_argument("--per-call-events", action="store_true",
                     help="A/B only: a timing event pair around every timed call (round-1 method)")
     ap.add_argument("--c3-certs", type=int, default=10000, help="C3 certificates per round")
@@ -1503,6 +1515,36 @@ def timed_steps(step, steps, warmup, world, dist, sync, before_timed=None, local
     return sharding.max_over_ranks(elapsed, dist, None)
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, verdicts, rank=0, world=1):
+    """--dump-outputs: what the timed path returned in its last step -- the
+    verify call's answer for every triple, as a caller of Signature::verify
+    reads it (coa_crypto.verify_strict_many(...) == 0): 1.0 where the call
+    accepted the signature (verdict 0, Ok), 0.0 where it rejected it -- as
+    float32 in DIR/accepted.npy (rank r > 0 of N: DIR/accepted_rank<r>.npy).
+    On the benchmark's all-valid workload a correct build writes all ones,
+    and the verdict buffer is set to Err before the timed steps, so a call
+    that wrote nothing shows as zeros.  The inputs are seeded (workloads.py)
+    and the signatures deterministic, so two builds run with the same
+    arguments can be compared output for output.  Above the size limit a
+    fixed, seeded sample of the indices is written (the same sample for the
+    same n), with the indices beside it."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    v = (np.asarray(verdicts) == 0).astype(np.float32)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    budget = DUMP_MAX_BYTES // max(1, world) - 4096  # room for the .npy headers
+    if v.nbytes > budget:
+        # 4 B per answer and 8 B per index
+        idx = np.sort(np.random.default_rng(0).choice(v.size, budget // 12, replace=False))
+        np.save(os.path.join(out_dir, f"accepted_sample_index{suffix}.npy"), idx.astype(np.float64))
+        v = v[idx]
+    np.save(os.path.join(out_dir, f"accepted{suffix}.npy"), v)
+
+
 def _latc():
     """tools/latc.c (lib/liblatc.so): the same one-item calls timed in a C
     loop, as the Rust crate's extern "C" binding makes them (no Python
@@ -1609,9 +1651,9 @@ def summarize(value, sec, cpu):
     configs' figures.  Every value is copied from `secondary` (None where a
     section did not run)."""
     if not sec:
-        # N > 1 (or --no-secondary): the secondary sections run on rank 0 at
-        # N = 1 only
-        out = {"c2_verify_per_s": round(value, 1), "secondary": "not run (N > 1 or --no-secondary)"}
+        # no --full, N > 1 or --no-secondary: the secondary sections run on
+        # rank 0 at N = 1 under --full only
+        out = {"c2_verify_per_s": round(value, 1), "secondary": "not run (no --full, N > 1 or --no-secondary)"}
         if cpu:
             out["cpu_c2_verify_per_s"] = cpu.get("value")
         return out
@@ -1898,6 +1940,8 @@ def main(argv=None):
     else:
         verify_ms = ev0.elapsed_time(ev1) / args.steps  # per call, HIP events on the calls' stream
     ok = int(verdicts.sum().item()) == 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, verdicts.cpu().numpy(), rank, world)
     props = torch.cuda.get_device_properties(local)
     ranks = gather_ranks({"rank": rank, "device": local,
                           "pci_bus": f"{props.pci_domain_id:04x}:{props.pci_bus_id:02x}:{props.pci_device_id:02x}",
@@ -1941,11 +1985,13 @@ def main(argv=None):
         roof["traffic"] = None
         roof["counters"] = f"no counter profile for this build: {pmc_why}"
 
+    # a plain run ends with the headline; the CPU baselines and the secondary
+    # sections are --full's
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(msgs_h, pks.cpu().numpy(), sigs.cpu().numpy(), args.cpu_thread_seconds)
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         threads = usable_cpus()
         del ws
         torch.cuda.empty_cache()

@@ -102,6 +102,44 @@ def test_gpus_flag_failing_rank_fails_the_run(monkeypatch, capfd):
     assert e.value.code == 3
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` asks for neither the
+    CPU baselines nor the secondary sections; --full does."""
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None
+    assert plain.steps == 7 and plain.warmup == 2
+    full = bench.parse(["--full", "--dump-outputs", "d"])
+    assert full.full is True and full.dump_outputs == "d"
+    s = bench.summarize(1.0, None, None)
+    assert s["c2_verify_per_s"] == 1.0 and "not run" in s["secondary"]
+
+
+def test_dump_outputs_writes_float32_answers(tmp_path, monkeypatch):
+    import numpy as np
+
+    v = np.zeros(1000, np.uint8)
+    v[[3, 999]] = 1
+    d = tmp_path / "a" / "b"  # created on demand
+    bench.dump_outputs(str(d), v)
+    got = np.load(d / "accepted.npy")
+    assert got.dtype == np.float32 and got.shape == (1000,)
+    # 1.0 where the call answered Ok (verdict 0), 0.0 where it rejected
+    assert np.array_equal(got, (v == 0).astype(np.float32))
+    assert got.sum() == 998 and got[3] == 0 and got[999] == 0
+    bench.dump_outputs(str(d), v, rank=1, world=2)
+    assert np.array_equal(np.load(d / "accepted_rank1.npy"), got)
+    # above the size limit: the same seeded sample of the indices every time
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096 + 12 * 100)
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / sub), v)
+    idx = np.load(tmp_path / "s1" / "accepted_sample_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and len(set(idx)) == 100
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "accepted_sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "accepted.npy"), got[idx.astype(np.int64)])
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= bench.DUMP_MAX_BYTES
+
+
 def test_c3_roofline_from_committed_counters():
     """summary.c3_roofline: the built algorithm's INT32
     count per certificate, and -- from profiles/r06_c3_pmc.json, tied by
