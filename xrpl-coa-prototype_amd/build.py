@@ -61,7 +61,42 @@ def build(verbose=False):
         if verbose:
             print("built", LIB)
     _build_latc()
+    _build_arithcheck()
     return LIB
+
+
+ARITH_SRC = os.path.join(ROOT, "tests", "arith", "arith_check.hip")
+ARITH_LIB = os.path.join(LIBDIR, "libcoa_arithcheck.so")
+ARITH_HEADERS = ["coa_fe.h", "coa_fe_wave.h", "coa_sc.h", "coa_halve.h", "coa_lehmer.h", "coa_ge.h"]
+
+
+def _build_arithcheck():
+    """lib/libcoa_arithcheck.so: the test-only kernels of
+    tests/arith/arith_check.hip around the arithmetic headers (no C-ABI
+    entry).  The source is compiled twice with the engine's COMMON flags, as
+    is and with -DCOA_RARE_INLINE, so both assembled forms of the rare carry
+    blocks of coa_fe.h are in it (symbols *_out / *_inl)."""
+    if not os.path.exists(ARITH_SRC):
+        return
+    deps = [ARITH_SRC, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ARITH_HEADERS]
+    if os.path.exists(ARITH_LIB) and os.path.getmtime(ARITH_LIB) >= _newest(deps):
+        return
+
+    def one(variant):
+        obj = os.path.join(OBJDIR, f"arith_check_{variant}.o")
+        cmd = [HIPCC] + COMMON + ["-I" + CSRC] + (["-DCOA_RARE_INLINE"] if variant == "inl" else []) + \
+              ["-c", ARITH_SRC, "-o", obj]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed for arith_check.hip ({variant}):\n{r.stderr[-6000:]}")
+        return obj
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=2) as ex:
+        objs = list(ex.map(one, ["out", "inl"]))
+    cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ARITH_LIB] + objs
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"libcoa_arithcheck link failed:\n{r.stderr[-6000:]}")
 
 
 def _build_latc():
