@@ -49,11 +49,18 @@ def _compile(src):
 def build(verbose=False):
     """Compile (incrementally) and link; returns the library path."""
     os.makedirs(OBJDIR, exist_ok=True)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
-        results = list(ex.map(_compile, SOURCES))
+    srcs = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "coa_verify.h")]
+    if os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(srcs) and \
+            not all(os.path.exists(os.path.join(OBJDIR, s + ".o")) for s in SOURCES):
+        # a tree that was copied with its library but without the object files:
+        # the library is newer than every source, so it is the build
+        results = []
+    else:
+        with concurrent.futures.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+            results = list(ex.map(_compile, SOURCES))
     objs = [o for o, _ in results]
     rebuilt = any(b for _, b in results)
-    if rebuilt or not os.path.exists(LIB) or os.path.getmtime(LIB) < _newest(objs):
+    if results and (rebuilt or not os.path.exists(LIB) or os.path.getmtime(LIB) < _newest(objs)):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-pthread", "-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
@@ -65,38 +72,50 @@ def build(verbose=False):
     return LIB
 
 
-ARITH_SRC = os.path.join(ROOT, "tests", "arith", "arith_check.hip")
-ARITH_LIB = os.path.join(LIBDIR, "libcoa_arithcheck.so")
-ARITH_HEADERS = ["coa_fe.h", "coa_fe_wave.h", "coa_sc.h", "coa_halve.h", "coa_lehmer.h", "coa_ge.h"]
+ARITH_HEADERS = ["coa_fe.h", "coa_fe_wave.h", "coa_sc.h", "coa_halve.h", "coa_lehmer.h", "coa_ge.h", "coa_smul.h",
+                 "coa_halved.h"]
+# test-only device libraries around the arithmetic headers: (source under tests/arith/, library under lib/)
+ARITH_LIBS = [("arith_check.hip", "libcoa_arithcheck.so"), ("alias_check.hip", "libcoa_aliascheck.so")]
+ARITH_SRC = os.path.join(ROOT, "tests", "arith", ARITH_LIBS[0][0])
+ARITH_LIB = os.path.join(LIBDIR, ARITH_LIBS[0][1])
 
 
 def _build_arithcheck():
-    """lib/libcoa_arithcheck.so: the test-only kernels of
-    tests/arith/arith_check.hip around the arithmetic headers (no C-ABI
-    entry).  The source is compiled twice with the engine's COMMON flags, as
+    """lib/libcoa_arithcheck.so and lib/libcoa_aliascheck.so: the test-only
+    kernels of tests/arith/*.hip around the arithmetic headers (no C-ABI
+    entry).  Each source is compiled twice with the engine's COMMON flags, as
     is and with -DCOA_RARE_INLINE, so both assembled forms of the rare carry
-    blocks of coa_fe.h are in it (symbols *_out / *_inl)."""
-    if not os.path.exists(ARITH_SRC):
-        return
-    deps = [ARITH_SRC, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ARITH_HEADERS]
-    if os.path.exists(ARITH_LIB) and os.path.getmtime(ARITH_LIB) >= _newest(deps):
+    blocks of coa_fe.h are in its library (symbols *_out / *_inl)."""
+    todo = []
+    for src_name, lib_name in ARITH_LIBS:
+        src, lib = os.path.join(ROOT, "tests", "arith", src_name), os.path.join(LIBDIR, lib_name)
+        if not os.path.exists(src):
+            continue
+        deps = [src, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ARITH_HEADERS]
+        if not (os.path.exists(lib) and os.path.getmtime(lib) >= _newest(deps)):
+            todo.append((src, lib))
+    if not todo:
         return
 
-    def one(variant):
-        obj = os.path.join(OBJDIR, f"arith_check_{variant}.o")
+    def one(job):
+        src, variant = job
+        stem = os.path.splitext(os.path.basename(src))[0]
+        obj = os.path.join(OBJDIR, f"{stem}_{variant}.o")
         cmd = [HIPCC] + COMMON + ["-I" + CSRC] + (["-DCOA_RARE_INLINE"] if variant == "inl" else []) + \
-              ["-c", ARITH_SRC, "-o", obj]
+              ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed for arith_check.hip ({variant}):\n{r.stderr[-6000:]}")
+            raise RuntimeError(f"hipcc failed for {os.path.basename(src)} ({variant}):\n{r.stderr[-6000:]}")
         return obj
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=2) as ex:
-        objs = list(ex.map(one, ["out", "inl"]))
-    cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", ARITH_LIB] + objs
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"libcoa_arithcheck link failed:\n{r.stderr[-6000:]}")
+    jobs = [(src, v) for src, _ in todo for v in ("out", "inl")]
+    with concurrent.futures.ThreadPoolExecutor(max_workers=len(jobs)) as ex:
+        objs = list(ex.map(one, jobs))
+    for k, (src, lib) in enumerate(todo):
+        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + objs[2 * k:2 * k + 2]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"{os.path.basename(lib)} link failed:\n{r.stderr[-6000:]}")
 
 
 def _build_latc():

@@ -24,6 +24,9 @@
 #include "coa_batch.h"
 #include "coa_kernels.h"
 
+// k_batch_terms (254 VGPRs, no spills) spills 7 dwords with the trimmed first
+// and last comba columns of coa_fe.h: this file keeps the uniform columns
+#define COA_COMBA_ALL_CARRIES
 #include "coa_fe.h"
 #include "coa_ge.h"
 #include "coa_sc.h"

@@ -125,6 +125,29 @@ COA_DEV void col(uint64_t& acc, uint32_t& c2, const uint32_t* x, const uint32_t*
 
 // Column k of a product: the pairs (i, k - i), 0 <= i, k - i < 8; for a
 // squaring only the cross products i < k - i.
+//
+// The first and the last column hold one product each and need no carry word:
+//  * first (K = 0; K = 1 of a squaring's cross sum): the accumulator is empty,
+//    so the column is the bare product, which fits its 64 bits; acc is written,
+//    not read (the caller need not clear it), and c2 = 0.
+//  * last (K = 14; K = 13 of the cross sum): nothing above the accumulator's
+//    two words exists.  A product a * b < 2^512 has 16 words, and after column
+//    14 the accumulator holds words 14 and 15, so the mad cannot carry out.
+//    The cross sum S = sum_{i<j} a_i a_j 2^(32(i+j)) has a_6 a_7 2^416 <=
+//    (2^32 - 1)^2 2^416 = 2^480 - 2^449 + 2^416 in column 13 and less than
+//    2^448 + 2^418 in all columns below (column 12 is a_5 a_7 2^384 < 2^448,
+//    column 11 two products < 2^417, and so on down), so S < 2^480:
+//    word 15 of S is 0 and the mad of column 13 cannot carry out either.
+//    c2 = 0 there is exact, and the v_addc that produced it fed nothing.
+// A translation unit whose kernel starts to spill with these forms (the
+// register allocator sees different live ranges) defines
+// COA_COMBA_ALL_CARRIES and keeps the uniform columns: coa_batch.hip, whose
+// k_batch_terms sits at 254 VGPRs.
+#ifdef COA_COMBA_ALL_CARRIES
+constexpr bool COA_COMBA_TRIM = false;
+#else
+constexpr bool COA_COMBA_TRIM = true;
+#endif
 template <int K, bool SQ>
 COA_DEV void mul_col(uint64_t& acc, uint32_t& c2, const fe& a, const fe& b) {
   constexpr int lo = K < 8 ? 0 : K - 7;
@@ -136,7 +159,17 @@ COA_DEV void mul_col(uint64_t& acc, uint32_t& c2, const fe& a, const fe& b) {
     x[p] = a.v[lo + p];
     y[p] = b.v[K - lo - p];
   }
-  if constexpr (P > 0) col<P>(acc, c2, x, y);
+  if constexpr (COA_COMBA_TRIM && K == (SQ ? 1 : 0)) {
+    static_assert(P == 1, "first column");
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc) : "v"(x[0]), "v"(y[0]) : "vcc");
+    c2 = 0;
+  } else if constexpr (COA_COMBA_TRIM && K == (SQ ? 13 : 14)) {
+    static_assert(P == 1, "last column");
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x[0]), "v"(y[0]) : "vcc");
+    c2 = 0;
+  } else if constexpr (P > 0) {
+    col<P>(acc, c2, x, y);
+  }
 }
 
 template <bool SQ, int K = SQ ? 1 : 0>
@@ -162,9 +195,21 @@ COA_DEV void fe_set(fe& r, uint32_t x) {
 // own code pads every such hand-off with `s_nop 1` on gfx950; at one wave per
 // SIMD (the C2 occupancy) that costs 1.6x (tools/ubench_carry.hip,
 // profiles/r01_ubench_carry.txt).
-#define COA_R8_INOUT(r)                                                                                    \
+//
+// fe_add / fe_sub / fe_addsub are out of place: both operands are inputs and
+// the result words are fresh early-clobber outputs, so a caller whose first
+// operand stays live pays no 8-register copy in front of the statement (a
+// move is an issue slot like any other for a wave alone on its SIMD).  Word i
+// of the result is written by instruction i while words > i of the operands
+// are still to be read, hence the early clobber; where the result aliases an
+// operand (fe_add(b, b, b), fe_sub(r.X, a, r.Y)) the compiler renames or, in
+// a loop, copies -- only there.
+#define COA_R8_INOUT(r)                                                                                   \
   "+&v"(r.v[0]), "+&v"(r.v[1]), "+&v"(r.v[2]), "+&v"(r.v[3]), "+&v"(r.v[4]), "+&v"(r.v[5]), "+&v"(r.v[6]), \
       "+&v"(r.v[7])
+#define COA_R8_OUT(r)                                                                                    \
+  "=&v"(r.v[0]), "=&v"(r.v[1]), "=&v"(r.v[2]), "=&v"(r.v[3]), "=&v"(r.v[4]), "=&v"(r.v[5]), "=&v"(r.v[6]), \
+      "=&v"(r.v[7])
 #define COA_B8_IN(b) \
   "v"(b.v[0]), "v"(b.v[1]), "v"(b.v[2]), "v"(b.v[3]), "v"(b.v[4]), "v"(b.v[5]), "v"(b.v[6]), "v"(b.v[7])
 
@@ -190,16 +235,16 @@ COA_DEV void fe_set(fe& r, uint32_t x) {
 // out-of-line block, COA_RARE_BEGIN); a carry out of that second
 // pass leaves words that wrapped to values < 38, so its fold cannot carry.
 COA_DEV void fe_add(fe& r, const fe& a, const fe& b) {
-  fe x = a;
+  fe x;
   uint32_t t;
-  asm("v_add_co_u32_e32 %0, vcc, %0, %9\n\t"
-      "v_addc_co_u32_e32 %1, vcc, %1, %10, vcc\n\t"
-      "v_addc_co_u32_e32 %2, vcc, %2, %11, vcc\n\t"
-      "v_addc_co_u32_e32 %3, vcc, %3, %12, vcc\n\t"
-      "v_addc_co_u32_e32 %4, vcc, %4, %13, vcc\n\t"
-      "v_addc_co_u32_e32 %5, vcc, %5, %14, vcc\n\t"
-      "v_addc_co_u32_e32 %6, vcc, %6, %15, vcc\n\t"
-      "v_addc_co_u32_e32 %7, vcc, %7, %16, vcc\n\t"
+  asm("v_add_co_u32_e32 %0, vcc, %9, %17\n\t"
+      "v_addc_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
+      "v_addc_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
+      "v_addc_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
+      "v_addc_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
+      "v_addc_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
+      "v_addc_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
+      "v_addc_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
       "v_cndmask_b32_e64 %8, 0, 38, vcc\n\t"
       "v_add_co_u32_e32 %0, vcc, %0, %8\n\t"
       COA_RARE_BEGIN
@@ -213,8 +258,8 @@ COA_DEV void fe_add(fe& r, const fe& a, const fe& b) {
       "v_cndmask_b32_e64 %8, 0, 38, vcc\n\t"
       "v_add_u32_e32 %0, %0, %8\n\t"
       COA_RARE_END
-      : COA_R8_INOUT(x), "=&v"(t)
-      : COA_B8_IN(b)
+      : COA_R8_OUT(x), "=&v"(t)
+      : COA_B8_IN(a), COA_B8_IN(b)
       : "vcc");
   r = x;
 }
@@ -223,16 +268,16 @@ COA_DEV void fe_add(fe& r, const fe& a, const fe& b) {
 // 2^256 == 38 subtracted once per borrow; the second borrow pass is behind
 // the same kind of wave-uniform branch as fe_add's.
 COA_DEV void fe_sub(fe& r, const fe& a, const fe& b) {
-  fe x = a;
+  fe x;
   uint32_t t;
-  asm("v_sub_co_u32_e32 %0, vcc, %0, %9\n\t"
-      "v_subb_co_u32_e32 %1, vcc, %1, %10, vcc\n\t"
-      "v_subb_co_u32_e32 %2, vcc, %2, %11, vcc\n\t"
-      "v_subb_co_u32_e32 %3, vcc, %3, %12, vcc\n\t"
-      "v_subb_co_u32_e32 %4, vcc, %4, %13, vcc\n\t"
-      "v_subb_co_u32_e32 %5, vcc, %5, %14, vcc\n\t"
-      "v_subb_co_u32_e32 %6, vcc, %6, %15, vcc\n\t"
-      "v_subb_co_u32_e32 %7, vcc, %7, %16, vcc\n\t"
+  asm("v_sub_co_u32_e32 %0, vcc, %9, %17\n\t"
+      "v_subb_co_u32_e32 %1, vcc, %10, %18, vcc\n\t"
+      "v_subb_co_u32_e32 %2, vcc, %11, %19, vcc\n\t"
+      "v_subb_co_u32_e32 %3, vcc, %12, %20, vcc\n\t"
+      "v_subb_co_u32_e32 %4, vcc, %13, %21, vcc\n\t"
+      "v_subb_co_u32_e32 %5, vcc, %14, %22, vcc\n\t"
+      "v_subb_co_u32_e32 %6, vcc, %15, %23, vcc\n\t"
+      "v_subb_co_u32_e32 %7, vcc, %16, %24, vcc\n\t"
       "v_cndmask_b32_e64 %8, 0, 38, vcc\n\t"
       "v_sub_co_u32_e32 %0, vcc, %0, %8\n\t"
       COA_RARE_BEGIN
@@ -246,8 +291,8 @@ COA_DEV void fe_sub(fe& r, const fe& a, const fe& b) {
       "v_cndmask_b32_e64 %8, 0, 38, vcc\n\t"
       "v_sub_u32_e32 %0, %0, %8\n\t"
       COA_RARE_END
-      : COA_R8_INOUT(x), "=&v"(t)
-      : COA_B8_IN(b)
+      : COA_R8_OUT(x), "=&v"(t)
+      : COA_B8_IN(a), COA_B8_IN(b)
       : "vcc");
   r = x;
 }
@@ -282,25 +327,25 @@ COA_DEV void fe_fold_word(fe& r, uint32_t w) {
 // compiler-held SCC (a loop condition) live across the statement would
 // otherwise be lost -- without it k_verify_main never left its digit loop.
 COA_DEV void fe_addsub(fe& s, fe& d, const fe& a, const fe& b) {
-  fe x = a, y = a;
+  fe x, y;
   uint32_t t, u;
   uint64_t cs, cd;
-  asm("v_add_co_u32_e64 %0, %[cs], %0, %[b0]\n\t"
-      "v_sub_co_u32_e64 %8, %[cd], %8, %[b0]\n\t"
-      "v_addc_co_u32_e64 %1, %[cs], %1, %[b1], %[cs]\n\t"
-      "v_subb_co_u32_e64 %9, %[cd], %9, %[b1], %[cd]\n\t"
-      "v_addc_co_u32_e64 %2, %[cs], %2, %[b2], %[cs]\n\t"
-      "v_subb_co_u32_e64 %10, %[cd], %10, %[b2], %[cd]\n\t"
-      "v_addc_co_u32_e64 %3, %[cs], %3, %[b3], %[cs]\n\t"
-      "v_subb_co_u32_e64 %11, %[cd], %11, %[b3], %[cd]\n\t"
-      "v_addc_co_u32_e64 %4, %[cs], %4, %[b4], %[cs]\n\t"
-      "v_subb_co_u32_e64 %12, %[cd], %12, %[b4], %[cd]\n\t"
-      "v_addc_co_u32_e64 %5, %[cs], %5, %[b5], %[cs]\n\t"
-      "v_subb_co_u32_e64 %13, %[cd], %13, %[b5], %[cd]\n\t"
-      "v_addc_co_u32_e64 %6, %[cs], %6, %[b6], %[cs]\n\t"
-      "v_subb_co_u32_e64 %14, %[cd], %14, %[b6], %[cd]\n\t"
-      "v_addc_co_u32_e64 %7, %[cs], %7, %[b7], %[cs]\n\t"
-      "v_subb_co_u32_e64 %15, %[cd], %15, %[b7], %[cd]\n\t"
+  asm("v_add_co_u32_e64 %0, %[cs], %[a0], %[b0]\n\t"
+      "v_sub_co_u32_e64 %8, %[cd], %[a0], %[b0]\n\t"
+      "v_addc_co_u32_e64 %1, %[cs], %[a1], %[b1], %[cs]\n\t"
+      "v_subb_co_u32_e64 %9, %[cd], %[a1], %[b1], %[cd]\n\t"
+      "v_addc_co_u32_e64 %2, %[cs], %[a2], %[b2], %[cs]\n\t"
+      "v_subb_co_u32_e64 %10, %[cd], %[a2], %[b2], %[cd]\n\t"
+      "v_addc_co_u32_e64 %3, %[cs], %[a3], %[b3], %[cs]\n\t"
+      "v_subb_co_u32_e64 %11, %[cd], %[a3], %[b3], %[cd]\n\t"
+      "v_addc_co_u32_e64 %4, %[cs], %[a4], %[b4], %[cs]\n\t"
+      "v_subb_co_u32_e64 %12, %[cd], %[a4], %[b4], %[cd]\n\t"
+      "v_addc_co_u32_e64 %5, %[cs], %[a5], %[b5], %[cs]\n\t"
+      "v_subb_co_u32_e64 %13, %[cd], %[a5], %[b5], %[cd]\n\t"
+      "v_addc_co_u32_e64 %6, %[cs], %[a6], %[b6], %[cs]\n\t"
+      "v_subb_co_u32_e64 %14, %[cd], %[a6], %[b6], %[cd]\n\t"
+      "v_addc_co_u32_e64 %7, %[cs], %[a7], %[b7], %[cs]\n\t"
+      "v_subb_co_u32_e64 %15, %[cd], %[a7], %[b7], %[cd]\n\t"
       "v_cndmask_b32_e64 %[t], 0, 38, %[cs]\n\t"
       "v_cndmask_b32_e64 %[u], 0, 38, %[cd]\n\t"
       "v_add_co_u32_e64 %0, %[cs], %0, %[t]\n\t"
@@ -326,9 +371,11 @@ COA_DEV void fe_addsub(fe& s, fe& d, const fe& a, const fe& b) {
       "v_add_u32_e32 %0, %0, %[t]\n\t"
       "v_sub_u32_e32 %8, %8, %[u]\n\t"
       COA_RARE_END
-      : COA_R8_INOUT(x), COA_R8_INOUT(y), [t] "=&v"(t), [u] "=&v"(u), [cs] "=&s"(cs), [cd] "=&s"(cd)
-      : [b0] "v"(b.v[0]), [b1] "v"(b.v[1]), [b2] "v"(b.v[2]), [b3] "v"(b.v[3]), [b4] "v"(b.v[4]),
-        [b5] "v"(b.v[5]), [b6] "v"(b.v[6]), [b7] "v"(b.v[7])
+      : COA_R8_OUT(x), COA_R8_OUT(y), [t] "=&v"(t), [u] "=&v"(u), [cs] "=&s"(cs), [cd] "=&s"(cd)
+      : [a0] "v"(a.v[0]), [a1] "v"(a.v[1]), [a2] "v"(a.v[2]), [a3] "v"(a.v[3]), [a4] "v"(a.v[4]),
+        [a5] "v"(a.v[5]), [a6] "v"(a.v[6]), [a7] "v"(a.v[7]), [b0] "v"(b.v[0]), [b1] "v"(b.v[1]),
+        [b2] "v"(b.v[2]), [b3] "v"(b.v[3]), [b4] "v"(b.v[4]), [b5] "v"(b.v[5]), [b6] "v"(b.v[6]),
+        [b7] "v"(b.v[7])
       : "vcc", "scc");  // s_or_b64 writes SCC
   s = x;
   d = y;

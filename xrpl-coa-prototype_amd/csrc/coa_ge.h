@@ -102,9 +102,24 @@ COA_DEV void ge_p3_dbl(ge_p1p1& r, const ge_p3& p) {
   ge_p2_dbl(r, q);
 }
 
+// r = c ? b : a and s = c ? a : b, word by word.
+COA_DEV void fe_cswap_to(fe& r, fe& s, const fe& a, const fe& b, bool c) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint32_t x = a.v[i], y = b.v[i];
+    r.v[i] = c ? y : x;
+    s.v[i] = c ? x : y;
+  }
+}
+
 // P + Q and P - Q with Q in cached form (add-2008-hwcd-3, k = 2d).
-COA_DEV void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
-  fe a, b, c, zz;
+// t2d_neg: the addend's T2d is to be taken negated (the T half of negating a
+// table entry, -(x, y) = (-x, y); its Y+X / Y-X halves were swapped by the
+// caller).  -T2d only flips the sign of c in Z = zz + c, T = zz - c, so the two
+// results trade places -- selects instead of a field negation of T2d and its
+// selects.
+COA_DEV void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q, bool t2d_neg = false) {
+  fe a, b, c, zz, zs, zd;
   fe_add(r.X, p.Y, p.X);
   fe_sub(r.Y, p.Y, p.X);
   fe_mul(b, r.X, q.YplusX);
@@ -114,8 +129,9 @@ COA_DEV void ge_add(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
   fe_add(zz, zz, zz);
   fe_sub(r.X, b, a);
   fe_add(r.Y, b, a);
-  fe_add(r.Z, zz, c);
-  fe_sub(r.T, zz, c);
+  fe_add(zs, zz, c);
+  fe_sub(zd, zz, c);
+  fe_cswap_to(r.Z, r.T, zs, zd, t2d_neg);
 }
 COA_DEV void ge_sub(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
   fe a, b, c, zz;
@@ -180,8 +196,8 @@ COA_DEV void ge_p2_dbl_il(ge_p1p1& r, const ge_p2& p) {
   fe_sub(r.X, o[3], r.Y);
   fe_sub(r.T, o[2], r.Z);
 }
-COA_DEV void ge_add_il(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
-  fe a[4], o[4];
+COA_DEV void ge_add_il(ge_p1p1& r, const ge_p3& p, const ge_cached& q, bool t2d_neg = false) {  // as ge_add
+  fe a[4], o[4], zs, zd;
   fe_addsub(a[0], a[1], p.Y, p.X);
   a[2] = q.T2d;
   a[3] = p.Z;
@@ -189,7 +205,8 @@ COA_DEV void ge_add_il(ge_p1p1& r, const ge_p3& p, const ge_cached& q) {
   fe_mul_n<4>(o, a, b);
   fe_add(o[3], o[3], o[3]);
   fe_addsub(r.Y, r.X, o[0], o[1]);
-  fe_addsub(r.Z, r.T, o[3], o[2]);
+  fe_addsub(zs, zd, o[3], o[2]);
+  fe_cswap_to(r.Z, r.T, zs, zd, t2d_neg);
 }
 
 COA_DEV void ge_madd_il(ge_p1p1& r, const ge_p3& p, const ge_niels& q) {

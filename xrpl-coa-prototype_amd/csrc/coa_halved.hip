@@ -36,73 +36,6 @@
 namespace {
 using namespace coa_halve;
 
-// per-lane tables j*P, j = 1..8, for two bases; lane-major, 2 KiB per lane
-COA_DEV void tab2_store(uint32_t* scr, uint32_t lane, int tab, int entry, const ge_cached& q) {
-  const fe* f[4] = {&q.YplusX, &q.YminusX, &q.Z, &q.T2d};
-#pragma unroll
-  for (int c = 0; c < 4; c++)
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-      reinterpret_cast<uint4*>(scr)[((uint64_t)lane * 16 + tab * 8 + entry) * 8 + c * 2 + h] =
-          make_uint4(f[c]->v[4 * h], f[c]->v[4 * h + 1], f[c]->v[4 * h + 2], f[c]->v[4 * h + 3]);
-}
-
-COA_DEV void tab2_select(ge_cached& q, const uint32_t* scr, uint32_t lane, int tab, int d) {
-  const int m = d < 0 ? -d : d;
-  const int entry = m == 0 ? 0 : m - 1;
-  fe* f[4] = {&q.YplusX, &q.YminusX, &q.Z, &q.T2d};
-#pragma unroll
-  for (int c = 0; c < 4; c++)
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint4 v = reinterpret_cast<const uint4*>(scr)[((uint64_t)lane * 16 + tab * 8 + entry) * 8 + c * 2 + h];
-      f[c]->v[4 * h] = v.x;
-      f[c]->v[4 * h + 1] = v.y;
-      f[c]->v[4 * h + 2] = v.z;
-      f[c]->v[4 * h + 3] = v.w;
-    }
-  if (m == 0) ge_cached_identity(q);
-  ge_cached_cneg(q, d < 0);
-}
-
-// tab2_select in two halves: the raw entry load (issued early, so a lone
-// wave's doublings cover its latency) and the sign/zero fix-up at the use.
-COA_DEV void tab2_load(ge_cached& q, const uint32_t* scr, uint32_t lane, int tab, int d) {
-  const int m = d < 0 ? -d : d;
-  const int entry = m == 0 ? 0 : m - 1;
-  fe* f[4] = {&q.YplusX, &q.YminusX, &q.Z, &q.T2d};
-#pragma unroll
-  for (int c = 0; c < 4; c++)
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint4 v = reinterpret_cast<const uint4*>(scr)[((uint64_t)lane * 16 + tab * 8 + entry) * 8 + c * 2 + h];
-      f[c]->v[4 * h] = v.x;
-      f[c]->v[4 * h + 1] = v.y;
-      f[c]->v[4 * h + 2] = v.z;
-      f[c]->v[4 * h + 3] = v.w;
-    }
-}
-COA_DEV void tab2_fix(ge_cached& q, int d) {
-  if (d == 0) ge_cached_identity(q);
-  ge_cached_cneg(q, d < 0);
-}
-
-COA_DEV void tab2_build(uint32_t* scr, uint32_t lane, int tab, const ge_p3& P) {
-  ge_cached c1;
-  ge_p3_to_cached(c1, P);
-  tab2_store(scr, lane, tab, 0, c1);
-  ge_p3 cur = P;
-#pragma unroll 1
-  for (int j = 1; j < 8; j++) {
-    ge_p1p1 t;
-    ge_add(t, cur, c1);
-    ge_p1p1_to_p3(cur, t);
-    ge_cached cj;
-    ge_p3_to_cached(cj, cur);
-    tab2_store(scr, lane, tab, j, cj);
-  }
-}
-
 COA_DEV int wave_max(int v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
@@ -560,18 +493,16 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_main(const uint32_t* __re
         }
       }
       if constexpr (IL) {
-        tab2_fix(qa, dc);
-        ge_add_il(t, acc3, qa);
+        ge_add_il(t, acc3, qa, dc < 0);
         ge_p1p1_to_p3_il(acc3, t);
-        tab2_fix(qr, dr);
-        ge_add_il(t, acc3, qr);
+        ge_add_il(t, acc3, qr, dr < 0);
         if (pos != 0) ge_p1p1_to_p2_il(acc2, t);
       } else {
-        tab2_select(qa, scr, i, 0, dc);
-        ge_add(t, acc3, qa);
+        tab2_load(qa, scr, i, 0, dc);
+        ge_add(t, acc3, qa, dc < 0);
         ge_p1p1_to_p3(acc3, t);
-        tab2_select(qr, scr, i, 1, dr);
-        ge_add(t, acc3, qr);
+        tab2_load(qr, scr, i, 1, dr);
+        ge_add(t, acc3, qr, dr < 0);
         if (pos != 0) ge_p1p1_to_p2(acc2, t);
       }
     }
@@ -677,8 +608,7 @@ __global__ void __launch_bounds__(128, 2) k_verify_main2(const uint32_t* __restr
         ge_p2_dbl_il(t, acc2);
         ge_p1p1_to_p3_il(acc3, t);
       }
-      tab2_fix(q, dr);
-      ge_add_il(t, acc3, q);
+      ge_add_il(t, acc3, q, dr < 0);
       if (pos != 0) ge_p1p1_to_p2_il(acc2, t);
     }
     ge_p1p1_to_p3_il(acc3, t);
@@ -780,8 +710,8 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __r
         fe_neg(PR.X, R.X);
         fe_neg(PR.T, R.T);
       }
-      tab2_build(scr, lane, 0, PA);
-      tab2_build(scr, lane, 1, PR);
+      tab2_build_chain(scr, lane, 0, PA);
+      tab2_build_chain(scr, lane, 1, PR);
       ge_p3 acc3;
       ge_p2 acc2;
       ge_p1p1 t;
@@ -801,11 +731,11 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __r
           ge_p1p1_to_p3(acc3, t);
         }
         ge_cached q;
-        tab2_select(q, scr, lane, 0, dc);
-        ge_add(t, acc3, q);
+        tab2_load(q, scr, lane, 0, dc);
+        ge_add(t, acc3, q, dc < 0);
         ge_p1p1_to_p3(acc3, t);
-        tab2_select(q, scr, lane, 1, dd);
-        ge_add(t, acc3, q);
+        tab2_load(q, scr, lane, 1, dd);
+        ge_add(t, acc3, q, dd < 0);
         if (pos != 0) ge_p1p1_to_p2(acc2, t);
       }
       ge_p1p1_to_p3(acc3, t);

@@ -232,3 +232,111 @@ COA_DEV uint32_t take_low_byte(uint32_t* x) {
   return lo;
 }
 
+// ---------------------------------------------------------------------------
+// Per-item slab tables of the halved verification (coa_halved.hip): j*P,
+// j = 1..8, in cached form, for an item's two bases (-A and -R); lane-major,
+// 2 KiB per item (COA_HALVED_SCRATCH_PER_LANE).
+// ---------------------------------------------------------------------------
+COA_DEV void tab2_store(uint32_t* scr, uint32_t lane, int tab, int entry, const ge_cached& q) {
+  const fe* f[4] = {&q.YplusX, &q.YminusX, &q.Z, &q.T2d};
+#pragma unroll
+  for (int c = 0; c < 4; c++)
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+      reinterpret_cast<uint4*>(scr)[((uint64_t)lane * 16 + tab * 8 + entry) * 8 + c * 2 + h] =
+          make_uint4(f[c]->v[4 * h], f[c]->v[4 * h + 1], f[c]->v[4 * h + 2], f[c]->v[4 * h + 3]);
+}
+
+// The identity in cached form, (Y+X, Y-X, Z, 2dT) = (1, 1, 1, 0): the entry a
+// zero digit reads.  Never written, but not declared const: a const array goes
+// to the constant address space, and a lane's choice between it and the slab
+// (global) would make every table load a flat load.
+static __device__ uint32_t tab2_identity[32] __attribute__((aligned(16))) = {
+    1, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// Entry |d| of a table for the signed digit d, the identity for d == 0: the
+// lane's address is the entry's or tab2_identity's (two selects on the address
+// instead of 32 on the loaded words).  -(x, y) = (-x, y) swaps Y+X / Y-X and
+// negates T2d.  The swap is done by the load as well: for d < 0 each of the
+// two takes the other's address (their uint4 indices 0..1 and 2..3 differ in
+// bit 1).  T2d comes back as stored: the caller hands d < 0 to ge_add /
+// ge_add_il, where -T2d is a swap of two results, not a field negation.  So
+// nothing is left to fix at the use, and the load can be issued early (a lone
+// wave's doublings cover its latency).
+COA_DEV void tab2_load(ge_cached& q, const uint32_t* scr, uint32_t lane, int tab, int d) {
+  const int m = d < 0 ? -d : d;
+  const uint4* e = reinterpret_cast<const uint4*>(scr) + ((uint64_t)lane * 16 + tab * 8 + (m == 0 ? 0 : m - 1)) * 8;
+  const uint4* src = m == 0 ? reinterpret_cast<const uint4*>(tab2_identity) : e;
+  const int sw = d < 0 ? 2 : 0;
+  fe* f[4] = {&q.YplusX, &q.YminusX, &q.Z, &q.T2d};
+#pragma unroll
+  for (int c = 0; c < 4; c++)
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const uint4 v = src[(c * 2 + h) ^ (c < 2 ? sw : 0)];
+      f[c]->v[4 * h] = v.x;
+      f[c]->v[4 * h + 1] = v.y;
+      f[c]->v[4 * h + 2] = v.z;
+      f[c]->v[4 * h + 3] = v.w;
+    }
+}
+
+// The table j*P, j = 1..8, of a decompressed point P (Z = 1, so its cached
+// form is also its affine Niels form).  Pass k = 1..4 stores 2k*P = 2 (k*P)
+// (a doubling, 4S + 4M) and, for k < 4, (2k+1)*P = 2k*P + P (a mixed addition,
+// 7M): 16S + 45M with the eight 2d*T products, against 64M for seven full
+// additions.  k*P waits in a two-deep queue of projective points: 2P and 3P
+// after pass 1, 3P and 4P after pass 2, 4P after pass 3.
+COA_DEV void tab2_build(uint32_t* scr, uint32_t lane, int tab, const ge_p3& P) {
+  ge_cached c;
+  ge_p3_to_cached(c, P);
+  tab2_store(scr, lane, tab, 0, c);
+  ge_niels n1;
+  n1.yplusx = c.YplusX;
+  n1.yminusx = c.YminusX;
+  n1.xy2d = c.T2d;
+  ge_p2 q0, q1;
+  ge_p3_to_p2(q0, P);
+  q1 = q0;
+#pragma unroll 1
+  for (int k = 1; k <= 4; k++) {
+    ge_p1p1 t;
+    ge_p3 e;
+    ge_p2_dbl(t, q0);
+    ge_p1p1_to_p3(e, t);
+    ge_p3_to_cached(c, e);
+    tab2_store(scr, lane, tab, 2 * k - 1, c);
+    if (k == 1) {
+      ge_p3_to_p2(q0, e);
+    } else {
+      q0 = q1;
+      if (k == 2) ge_p3_to_p2(q1, e);
+    }
+    if (k < 4) {
+      ge_madd(t, e, n1);
+      ge_p1p1_to_p3(e, t);
+      ge_p3_to_cached(c, e);
+      tab2_store(scr, lane, tab, 2 * k, c);
+      if (k == 1) ge_p3_to_p2(q1, e);
+    }
+  }
+}
+
+// The same table by seven full additions of P (any Z): one live point instead
+// of tab2_build's queue, for the one-kernel path (k_verify_halved), which
+// already spills at its register bound and would spill more with the queue.
+COA_DEV void tab2_build_chain(uint32_t* scr, uint32_t lane, int tab, const ge_p3& P) {
+  ge_cached c1;
+  ge_p3_to_cached(c1, P);
+  tab2_store(scr, lane, tab, 0, c1);
+  ge_p3 cur = P;
+#pragma unroll 1
+  for (int j = 1; j < 8; j++) {
+    ge_p1p1 t;
+    ge_add(t, cur, c1);
+    ge_p1p1_to_p3(cur, t);
+    ge_cached cj;
+    ge_p3_to_cached(cj, cur);
+    tab2_store(scr, lane, tab, j, cj);
+  }
+}
