@@ -250,6 +250,49 @@ int coa_certificate_verify_many_device(int device, const uint8_t* d_header_data,
                                        const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
                                        size_t n_votes, uint32_t* d_status, void* workspace, void* stream);
 
+/* ------------------------------- Header::verify / Vote::verify crypto
+ * The crypto of Header::verify (primary/src/messages.rs:48-67: the digest
+ * check :49-51 and Signature::verify(header.id, author) :64-66) and of
+ * Vote::verify (:131-142: Signature::verify(Vote::digest, author) :139-141,
+ * Vote::digest = SHA-512(id || round u64 LE || origin)[..32], :145-153) for
+ * many messages in ONE launch with the registered committee's key combs (no
+ * doubling, no decompression of A or R).  The reference checks
+ * committee.stake(author) > 0 before either signature, so every signature
+ * that matters is by a registered key; the others are re-decided through the
+ * uncached entry points (SHA-512 + coa_ed25519_verify_strict_many), so the
+ * answer is always dalek's verify_strict, registered or not, and with no
+ * committee registered every item takes that route.  The non-crypto checks
+ * (stake, worker ids, round) stay with the caller.
+ * The arrays are what coa_wire_decode_headers / coa_wire_decode_votes fill:
+ *   header_data/header_offsets  n + 1 offsets into the concatenated
+ *                               Header::digest inputs
+ *   ids, authors                n * 32;  sigs n * 64 (R || s)
+ *   rounds, origins             n, n * 32 (votes: the voted header's round
+ *                               and author)
+ *   status_out[i]   (headers)   0, or COA_CERT_BAD_HEADER_ID |
+ *                               COA_CERT_BAD_HEADER_SIG
+ *   verdicts_out[i] (votes)     0 Ok / 1 Err
+ * Host forms shard by contiguous index range over the opened devices; n = 0
+ * returns COA_OK. */
+int coa_header_verify_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                           const uint8_t* authors, const uint8_t* sigs, size_t n, uint8_t* status_out);
+int coa_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                         const uint8_t* sigs, size_t n, uint8_t* verdicts_out);
+/* Device-resident forms (asynchronous on `stream`; NULL = the engine's
+ * stream): d_status[i], zeroed by the call, receives the raw word -- bit 1
+ * (headers) the digest differs from ids[i], bit 2 the signature fails
+ * verify_strict, bit 16 the author is not registered and nothing else was
+ * decided for the item (use the uncached entry points).  `workspace`: NULL
+ * (engine-owned; the call then waits for its stream) or at least
+ * coa_message_workspace_bytes(n) bytes of device memory. */
+size_t coa_message_workspace_bytes(size_t n);
+int coa_header_verify_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                  const uint8_t* d_ids, const uint8_t* d_authors, const uint8_t* d_sigs, size_t n,
+                                  uint32_t* d_status, void* workspace, void* stream);
+int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
+                                const uint8_t* d_authors, const uint8_t* d_sigs, size_t n, uint32_t* d_status,
+                                void* workspace, void* stream);
+
 /* ------------------------------------------------------- wire decode (f4)
  * bincode 1.3 decode of PrimaryMessage frames, as
  * PrimaryReceiverHandler::dispatch does (primary/src/primary.rs:223-244),
@@ -314,7 +357,11 @@ int coa_ed25519_sign_many_device(int device, const uint8_t* d_seeds, const uint8
  *                                      primary/src/messages.rs:70-84,226-234
  *   coa_cpu_certificate_verify_many[_z]  primary/src/messages.rs:189-215
  *                                      (status_out: COA_CERT_* bits; _z takes
- *                                      the votes' 16-byte weights) */
+ *                                      the votes' 16-byte weights)
+ *   coa_cpu_header_verify_many         primary/src/messages.rs:49-51,64-66
+ *   coa_cpu_vote_verify_many           primary/src/messages.rs:139-153
+ *                                      (arguments and outputs as the GPU host
+ *                                      forms above) */
 int coa_cpu_ed25519_verify_strict(const uint8_t* msg, size_t msg_len, const uint8_t pk[32], const uint8_t sig[64]);
 int coa_cpu_ed25519_verify_strict_many(const uint8_t* msgs, size_t msg_len, const uint8_t* pks, const uint8_t* sigs,
                                        size_t n, uint8_t* verdicts_out, int nthreads);
@@ -332,6 +379,11 @@ int coa_cpu_certificate_verify_many_z(const uint8_t* header_data, const uint64_t
                                       const uint8_t* origins, const uint8_t* header_sigs, const uint64_t* rounds,
                                       const uint8_t* vote_pks, const uint8_t* vote_sigs, const uint64_t* vote_offsets,
                                       size_t n, const uint8_t* zs, uint8_t* status_out, int nthreads);
+int coa_cpu_header_verify_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                               const uint8_t* authors, const uint8_t* sigs, size_t n, uint8_t* status_out,
+                               int nthreads);
+int coa_cpu_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                             const uint8_t* sigs, size_t n, uint8_t* verdicts_out, int nthreads);
 
 /* ------------------------------------------------ aggregation queue (f1)
  * Pre-verification stage for Core::run (primary/src/core.rs:349-389), which

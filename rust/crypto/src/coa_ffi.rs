@@ -151,6 +151,21 @@ extern "C" {
                                               n_votes: usize, d_status: *mut u32, workspace: *mut c_void,
                                               stream: *mut c_void) -> c_int;
 
+    // ------------------------------- Header::verify / Vote::verify crypto
+    pub fn coa_header_verify_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                  authors: *const u8, sigs: *const u8, n: usize, status_out: *mut u8) -> c_int;
+    pub fn coa_vote_verify_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
+                                sigs: *const u8, n: usize, verdicts_out: *mut u8) -> c_int;
+    pub fn coa_message_workspace_bytes(n: usize) -> usize;
+    pub fn coa_header_verify_many_device(device: c_int, d_header_data: *const u8, d_header_offsets: *const u64,
+                                         d_ids: *const u8, d_authors: *const u8, d_sigs: *const u8, n: usize,
+                                         d_status: *mut u32, workspace: *mut c_void,
+                                         stream: *mut c_void) -> c_int;
+    pub fn coa_vote_verify_many_device(device: c_int, d_ids: *const u8, d_rounds: *const u64,
+                                       d_origins: *const u8, d_authors: *const u8, d_sigs: *const u8, n: usize,
+                                       d_status: *mut u32, workspace: *mut c_void,
+                                       stream: *mut c_void) -> c_int;
+
     // --------------------------------------------------- wire decode (f4)
     pub fn coa_wire_scan(frames: *const u8, frame_offsets: *const u64, n: usize, kind_out: *mut i32,
                          header_bytes_out: *mut u64, votes_out: *mut u64) -> c_int;
@@ -194,6 +209,11 @@ extern "C" {
                                              vote_pks: *const u8, vote_sigs: *const u8, vote_offsets: *const u64,
                                              n: usize, zs: *const u8, status_out: *mut u8,
                                              nthreads: c_int) -> c_int;
+    pub fn coa_cpu_header_verify_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                      authors: *const u8, sigs: *const u8, n: usize, status_out: *mut u8,
+                                      nthreads: c_int) -> c_int;
+    pub fn coa_cpu_vote_verify_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
+                                    sigs: *const u8, n: usize, verdicts_out: *mut u8, nthreads: c_int) -> c_int;
 
     // ------------------------------------------------- aggregation queue (f1)
     pub fn coa_queue_create(max_batch: usize, max_delay_us: u32) -> *mut CoaQueue;

@@ -127,6 +127,38 @@ pub fn cpu_digest(bytes: &[u8]) -> Digest {
     Digest(d)
 }
 
+/// The COA_CERT_BAD_HEADER_ID / COA_CERT_BAD_HEADER_SIG bits of
+/// `Header::verify`'s two crypto checks (primary/src/messages.rs:49-51,
+/// 64-66) for many headers on the engine's CPU path.  Arrays as
+/// `coa_header_verify_many` takes them: concatenated digest inputs with
+/// n + 1 offsets, 32-byte ids and authors, 64-byte signatures.
+pub fn cpu_header_bits(header_data: &[u8], header_offsets: &[u64], ids: &[u8], authors: &[u8], sigs: &[u8]) -> Vec<u8> {
+    let n = ids.len() / 32;
+    assert!(header_offsets.len() == n + 1 && authors.len() == 32 * n && sigs.len() == 64 * n);
+    let mut status = vec![0xffu8; n];
+    let rc = unsafe {
+        ffi::coa_cpu_header_verify_many(header_data.as_ptr(), header_offsets.as_ptr(), ids.as_ptr(), authors.as_ptr(),
+                                        sigs.as_ptr(), n, status.as_mut_ptr(), CPU_THREADS)
+    };
+    cpu_status(rc, "Header::verify (many)");
+    status
+}
+
+/// `Vote::verify`'s signature check (primary/src/messages.rs:139-141 over
+/// `Vote::digest`, :145-153) for many votes on the engine's CPU path: one
+/// verdict byte per vote, 0 Ok / 1 Err.
+pub fn cpu_vote_verdicts(ids: &[u8], rounds: &[u64], origins: &[u8], authors: &[u8], sigs: &[u8]) -> Vec<u8> {
+    let n = rounds.len();
+    assert!(ids.len() == 32 * n && origins.len() == 32 * n && authors.len() == 32 * n && sigs.len() == 64 * n);
+    let mut verdicts = vec![1u8; n];
+    let rc = unsafe {
+        ffi::coa_cpu_vote_verify_many(ids.as_ptr(), rounds.as_ptr(), origins.as_ptr(), authors.as_ptr(), sigs.as_ptr(),
+                                      n, verdicts.as_mut_ptr(), CPU_THREADS)
+    };
+    cpu_status(rc, "Vote::verify (many)");
+    verdicts
+}
+
 /// The COA_CERT_* bits of `Certificate::verify`'s three crypto checks
 /// (primary/src/messages.rs:48-67,189-215), each evaluated on its own as the
 /// engine reports them: bit 0 `Header::digest != id` (:70-84), bit 1 the

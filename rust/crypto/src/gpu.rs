@@ -162,6 +162,81 @@ pub fn verify_many(items: &[(Digest, PublicKey, [u8; 64])]) -> Vec<Result<(), Cr
     out.into_iter().map(|v| if v == 0 { Ok(()) } else { Err(CryptoError::new()) }).collect()
 }
 
+/// One `Header` as `headers_verify_many` takes it: the `Header::digest` input
+/// bytes (primary/src/messages.rs:70-84), `id`, `author` and the 64-byte
+/// signature.
+pub struct HeaderItem<'a> {
+    pub digest_input: &'a [u8],
+    pub id: Digest,
+    pub author: PublicKey,
+    pub signature: [u8; 64],
+}
+
+/// One `Vote` as `votes_verify_many` takes it (primary/src/messages.rs:
+/// 120-153): the voted header's `id`, `round` and `origin`, the voter and
+/// the 64-byte signature.
+pub struct VoteItem {
+    pub id: Digest,
+    pub round: u64,
+    pub origin: PublicKey,
+    pub author: PublicKey,
+    pub signature: [u8; 64],
+}
+
+/// The crypto of `Header::verify` (primary/src/messages.rs:48-67) for a
+/// backlog of headers in ONE launch over the registered committee's key
+/// combs: per header the COA_CERT_BAD_HEADER_ID (bit 0, :49-51) and
+/// COA_CERT_BAD_HEADER_SIG (bit 1, :64-66) bits.  The caller applies them in
+/// the reference's order around its stake and worker-id checks.
+pub fn headers_verify_many(items: &[HeaderItem]) -> Vec<u8> {
+    let n = items.len();
+    let mut data = Vec::new();
+    let mut offsets = Vec::with_capacity(n + 1);
+    offsets.push(0u64);
+    let (mut ids, mut authors, mut sigs) = (Vec::with_capacity(32 * n), Vec::with_capacity(32 * n), Vec::with_capacity(64 * n));
+    for h in items {
+        data.extend_from_slice(h.digest_input);
+        offsets.push(data.len() as u64);
+        ids.extend_from_slice(&h.id.0);
+        authors.extend_from_slice(&h.author.0);
+        sigs.extend_from_slice(&h.signature);
+    }
+    data.push(0); // never a dangling pointer for an all-empty window
+    let mut out = vec![0xffu8; n];
+    if !engine_ok(unsafe {
+        ffi::coa_header_verify_many(data.as_ptr(), offsets.as_ptr(), ids.as_ptr(), authors.as_ptr(), sigs.as_ptr(), n,
+                                    out.as_mut_ptr())
+    }, "Header::verify (many)") {
+        return degrade::cpu_header_bits(&data, &offsets, &ids, &authors, &sigs);
+    }
+    out
+}
+
+/// The crypto of `Vote::verify` (primary/src/messages.rs:131-142) for a
+/// backlog of votes in ONE launch: `Vote::digest` is hashed on the device and
+/// checked by verify_strict under the voter's key.  One Ok/Err per vote; the
+/// caller's stake check comes first, as in the reference.
+pub fn votes_verify_many(items: &[VoteItem]) -> Vec<Result<(), CryptoError>> {
+    let n = items.len();
+    let (mut ids, mut origins, mut authors) = (Vec::with_capacity(32 * n), Vec::with_capacity(32 * n), Vec::with_capacity(32 * n));
+    let (mut rounds, mut sigs) = (Vec::with_capacity(n), Vec::with_capacity(64 * n));
+    for v in items {
+        ids.extend_from_slice(&v.id.0);
+        rounds.push(v.round);
+        origins.extend_from_slice(&v.origin.0);
+        authors.extend_from_slice(&v.author.0);
+        sigs.extend_from_slice(&v.signature);
+    }
+    let mut out = vec![1u8; n];
+    if !engine_ok(unsafe {
+        ffi::coa_vote_verify_many(ids.as_ptr(), rounds.as_ptr(), origins.as_ptr(), authors.as_ptr(), sigs.as_ptr(), n,
+                                  out.as_mut_ptr())
+    }, "Vote::verify (many)") {
+        out = degrade::cpu_vote_verdicts(&ids, &rounds, &origins, &authors, &sigs);
+    }
+    out.into_iter().map(|v| if v == 0 { Ok(()) } else { Err(CryptoError::new()) }).collect()
+}
+
 /// Many certificates' vote batches in one launch: one verify_batch verdict
 /// per group (certificate), votes concatenated, group g = votes of
 /// certificate g over digests[g].

@@ -16,7 +16,9 @@ host-side protocol checks, so the error raised is the reference's.
 `verify_stepwise` is the same method over the per-primitive entry points
 (verify_strict / verify_batch / Digest), kept for cross-checks.
 `verify_certificates` / `verify_certificate_batch` do the same for many
-certificates with one coa_certificate_verify_many call.
+certificates with one coa_certificate_verify_many call; `verify_headers` /
+`verify_votes` do it for a backlog of Header / Vote messages with one
+coa_header_verify_many / coa_vote_verify_many call each.
 """
 import struct
 
@@ -253,6 +255,52 @@ def verify_certificates(certs, committee, rng_seed=0):
             _raise_in_order(certs[i], committee, int(st[j]))
         except DagError as e:
             res[i] = e
+    return res
+
+
+def verify_headers(headers, committee):
+    """Header::verify (primary/src/messages.rs:48-67) for many headers: the
+    crypto of all of them in one coa_header_verify_many call, then the checks
+    in the reference's order.  Returns a list with None (Ok) or the DagError
+    instance."""
+    res = [None] * len(headers)
+    if not headers:
+        return res
+    ids = np.array([list(bytes(h.id)) for h in headers], np.uint8)
+    authors = np.array([list(bytes(h.author)) for h in headers], np.uint8)
+    sigs = np.array([list(h.signature.flatten()) for h in headers], np.uint8)
+    st = coa_crypto.header_verify_many([h.digest_input() for h in headers], ids, authors, sigs)
+    for i, h in enumerate(headers):
+        if st[i] & coa_crypto.CERT_BAD_HEADER_ID:                   # messages.rs:49-51
+            res[i] = InvalidHeaderId(h.id)
+        elif committee.stake(h.author) <= 0:                        # :53-56
+            res[i] = UnknownAuthority(h.author)
+        elif any(not committee.has_worker(h.author, wid) for wid in h.payload.values()):  # :58-62
+            res[i] = MalformedHeader(h.id)
+        elif st[i] & coa_crypto.CERT_BAD_HEADER_SIG:                # :64-66
+            res[i] = InvalidSignature()
+    return res
+
+
+def verify_votes(votes, committee):
+    """Vote::verify (primary/src/messages.rs:131-142) for many votes: one
+    coa_vote_verify_many call (Vote::digest is hashed on the device), then the
+    checks in the reference's order.  Returns a list with None (Ok) or the
+    DagError instance."""
+    res = [None] * len(votes)
+    if not votes:
+        return res
+    ids = np.array([list(bytes(v.id)) for v in votes], np.uint8)
+    origins = np.array([list(bytes(v.origin)) for v in votes], np.uint8)
+    authors = np.array([list(bytes(v.author)) for v in votes], np.uint8)
+    sigs = np.array([list(v.signature.flatten()) for v in votes], np.uint8)
+    rounds = np.array([v.round for v in votes], np.uint64)
+    verdicts = coa_crypto.vote_verify_many(ids, rounds, origins, authors, sigs)
+    for i, v in enumerate(votes):
+        if committee.stake(v.author) <= 0:                          # messages.rs:133-136
+            res[i] = UnknownAuthority(v.author)
+        elif verdicts[i]:                                           # :139-141
+            res[i] = InvalidSignature()
     return res
 
 

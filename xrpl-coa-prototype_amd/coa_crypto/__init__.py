@@ -137,6 +137,13 @@ def lib():
         "coa_certificate_workspace_bytes": ([sz, sz], sz),
         "coa_certificate_verify_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp],
                                                ctypes.c_int),
+        "coa_header_verify_many": ([P8, P64, P8, P8, P8, sz, P8], ctypes.c_int),
+        "coa_vote_verify_many": ([P8, P64, P8, P8, P8, sz, P8], ctypes.c_int),
+        "coa_message_workspace_bytes": ([sz], sz),
+        "coa_header_verify_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp], ctypes.c_int),
+        "coa_vote_verify_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp], ctypes.c_int),
+        "coa_cpu_header_verify_many": ([P8, P64, P8, P8, P8, sz, P8, ctypes.c_int], ctypes.c_int),
+        "coa_cpu_vote_verify_many": ([P8, P64, P8, P8, P8, sz, P8, ctypes.c_int], ctypes.c_int),
         "coa_wire_scan": ([P8, P64, sz, ctypes.POINTER(ctypes.c_int32), P64, P64], ctypes.c_int),
         "coa_wire_decode_certificates": ([P8, P64, sz, P8, P64, P8, P8, P8, P64, P8, P8, P64,
                                           ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
@@ -682,6 +689,91 @@ def certificate_verify_many_device(device, hdata, hoff, ids, origins, hsigs, rou
                                                     origins.data_ptr(), hsigs.data_ptr(), rounds.data_ptr(),
                                                     vpks.data_ptr(), vsigs.data_ptr(), voff.data_ptr(), n, nv,
                                                     status.data_ptr(), ws, _handle(device, stream)))
+
+
+# ------------------------------------ Header::verify / Vote::verify crypto
+def _header_arrays(header_inputs, ids, authors, sigs):
+    n = len(header_inputs)
+    hdata = np.frombuffer(b"".join(bytes(h) for h in header_inputs) + b"\0", np.uint8)
+    hoff = np.zeros(n + 1, np.uint64)
+    hoff[1:] = np.cumsum([len(h) for h in header_inputs])
+    ids, authors, sigs = (np.ascontiguousarray(a, dtype=np.uint8) for a in (ids, authors, sigs))
+    if ids.size != 32 * n or authors.size != 32 * n or sigs.size != 64 * n:
+        raise ValueError("one 32-byte id, 32-byte author and 64-byte signature per header")
+    return n, hdata, hoff, ids, authors, sigs
+
+
+def _vote_arrays(ids, rounds, origins, authors, sigs):
+    ids, origins, authors, sigs = (np.ascontiguousarray(a, dtype=np.uint8) for a in (ids, origins, authors, sigs))
+    n = ids.size // 32
+    rounds = np.ascontiguousarray(np.broadcast_to(np.asarray(rounds, np.uint64), (n,)))
+    if ids.size != 32 * n or origins.size != 32 * n or authors.size != 32 * n or sigs.size != 64 * n:
+        raise ValueError("one 32-byte id, origin and author and one 64-byte signature per vote")
+    return n, ids, rounds, origins, authors, sigs
+
+
+def header_verify_many(header_inputs, ids, authors, sigs):
+    """Crypto of Header::verify for n headers in one launch (the registered
+    committee's combs; authors outside it through the uncached kernels).
+    header_inputs: the Header::digest bytes of each.  Returns uint8 [n] of
+    CERT_BAD_HEADER_ID | CERT_BAD_HEADER_SIG bits (0 = both checks Ok)."""
+    n, hdata, hoff, ids, authors, sigs = _header_arrays(header_inputs, ids, authors, sigs)
+    out = np.full(max(n, 1), 0xff, np.uint8)
+    _check(lib().coa_header_verify_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(authors), _u8p(sigs), n, _u8p(out)))
+    return out[:n]
+
+
+def vote_verify_many(ids, rounds, origins, authors, sigs):
+    """Crypto of Vote::verify for n votes in one launch: verify_strict of
+    Vote::digest = SHA-512(id || round LE || origin)[..32] under the author.
+    Returns verdict bytes 0 Ok / 1 Err."""
+    n, ids, rounds, origins, authors, sigs = _vote_arrays(ids, rounds, origins, authors, sigs)
+    out = np.ones(max(n, 1), np.uint8)
+    _check(lib().coa_vote_verify_many(_u8p(ids), _u64p(rounds), _u8p(origins), _u8p(authors), _u8p(sigs), n,
+                                      _u8p(out)))
+    return out[:n]
+
+
+def cpu_header_verify_many(header_inputs, ids, authors, sigs, nthreads=0):
+    """CPU path of header_verify_many (explicit only; no coa_init needed)."""
+    n, hdata, hoff, ids, authors, sigs = _header_arrays(header_inputs, ids, authors, sigs)
+    out = np.full(max(n, 1), 0xff, np.uint8)
+    _check(lib().coa_cpu_header_verify_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(authors), _u8p(sigs), n,
+                                            _u8p(out), nthreads))
+    return out[:n]
+
+
+def cpu_vote_verify_many(ids, rounds, origins, authors, sigs, nthreads=0):
+    """CPU path of vote_verify_many (explicit only; no coa_init needed)."""
+    n, ids, rounds, origins, authors, sigs = _vote_arrays(ids, rounds, origins, authors, sigs)
+    out = np.ones(max(n, 1), np.uint8)
+    _check(lib().coa_cpu_vote_verify_many(_u8p(ids), _u64p(rounds), _u8p(origins), _u8p(authors), _u8p(sigs), n,
+                                          _u8p(out), nthreads))
+    return out[:n]
+
+
+def message_workspace_bytes(n):
+    return lib().coa_message_workspace_bytes(n)
+
+
+def header_verify_many_device(device, hdata, hoff, ids, authors, sigs, status, stream=None, workspace=None):
+    """Device-resident headers (torch tensors); raw status words (uint32
+    tensor [n]: CERT_BAD_HEADER_ID, CERT_BAD_HEADER_SIG, CERT_UNCACHED)
+    enqueued on `stream`.  workspace: None (engine-owned; the call waits for
+    the stream) or a device tensor of message_workspace_bytes(n)."""
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_header_verify_many_device(device, hdata.data_ptr(), hoff.data_ptr(), ids.data_ptr(),
+                                               authors.data_ptr(), sigs.data_ptr(), ids.shape[0], status.data_ptr(),
+                                               ws, _handle(device, stream)))
+
+
+def vote_verify_many_device(device, ids, rounds, origins, authors, sigs, status, stream=None, workspace=None):
+    """Device-resident votes; raw status words (CERT_BAD_HEADER_SIG = the
+    signature fails, CERT_UNCACHED = the author is not registered)."""
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_vote_verify_many_device(device, ids.data_ptr(), rounds.data_ptr(), origins.data_ptr(),
+                                             authors.data_ptr(), sigs.data_ptr(), ids.shape[0], status.data_ptr(), ws,
+                                             _handle(device, stream)))
 
 
 # ------------------------------------------------------------- wire (f4)

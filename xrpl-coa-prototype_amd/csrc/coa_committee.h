@@ -174,6 +174,37 @@ extern "C" int coa_certificate_verify_many_device_order(
     void* workspace, void* stream, int key_order);
 hipError_t coa_launch_cert_verify(CertArgs a, int lanes_per_sig, uint32_t* pscr, hipStream_t s);
 
+// Header::verify / Vote::verify crypto for many messages (k_msg_verify): one
+// strict signature job per message, the key tables named as in CertArgs.
+// Headers: hdr_data/hdr_off set, rounds null -- the message is ids[i] and the
+// leading blocks check SHA-512(Header::digest bytes)[..32] == ids[i].
+// Votes: rounds/origins set, hdr_data null -- the message is Vote::digest =
+// SHA-512(ids[i] || rounds[i] LE || origins[i])[..32], hashed in the job.
+struct MsgArgs {
+  const uint8_t* hdr_data;   // headers: Header::digest inputs, concatenated
+  const uint64_t* hdr_off;   // headers: [n + 1]
+  const uint32_t* ids;       // [n][8]  header.id / vote.id
+  const uint32_t* authors;   // [n][8]  the signer
+  const uint32_t* sigs;      // [n][16] R || s
+  const uint64_t* rounds;    // votes: [n]; null selects the header shape
+  const uint32_t* origins;   // votes: [n][8]
+  uint32_t n;
+  uint32_t hdr_blocks;       // set by the launcher
+  const uint32_t* keys;
+  const uint32_t* kflags;
+  const uint32_t* ktabs;
+  const uint32_t* kwtabs;
+  uint32_t kw20;
+  uint32_t nk;
+  const uint32_t* comb;
+  const uint32_t* wcomb;
+  uint32_t* status;          // [n], zeroed by the caller
+};
+// pscr: device scratch of coa_msg_scratch_bytes(a.n) bytes (the chunk counter
+// and the slab of the throughput grid, cert_tp_lanes)
+size_t coa_msg_scratch_bytes(uint64_t n);
+hipError_t coa_launch_msg_verify(MsgArgs a, uint32_t* pscr, hipStream_t s);
+
 // Row-parallel field arithmetic (coa_fe_wave.h) against coa_fe.h, one wave per
 // input x_i (32 LE bytes, any value < 2^256): out[i] bit0 pow_p58, bit1
 // invert, bit2 x_i * x_{i+1}, bit3 decompression of x_i as an encoding

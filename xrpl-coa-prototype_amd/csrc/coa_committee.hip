@@ -157,40 +157,81 @@ COA_DEV const uint32_t* sel_ptr(bool c, const uint32_t* p, const uint32_t* q) {
   return reinterpret_cast<const uint32_t*>(c ? reinterpret_cast<uintptr_t>(p) : reinterpret_cast<uintptr_t>(q));
 }
 
-COA_DEV void job_comb(const CertArgs& a, uint32_t job, ge_p3& P, uint32_t& pre, uint32_t& cert) {
+// msg <- SHA-512(msg || round u64 LE || origin)[..32]: Certificate::digest
+// (messages.rs:226-234) and Vote::digest (messages.rs:145-153)
+COA_DEV void round_origin_digest(uint32_t* msg, uint64_t rd, const uint32_t* origin) {
+  uint64_t st[8];
+  uint32_t h[16];
+  uint32_t in[18];
+#pragma unroll
+  for (int i = 0; i < 8; i++) in[i] = msg[i];
+  in[8] = (uint32_t)rd;
+  in[9] = (uint32_t)(rd >> 32);
+  load8(in + 10, origin);
+  coa_sha::hash_words<18>(st, in);
+  coa_sha::state_to_le_words(h, st);
+#pragma unroll
+  for (int i = 0; i < 8; i++) msg[i] = h[i];
+}
+
+// What differs between the kernels' jobs: job_load fetches a job's key, R, s
+// and 32-byte message id and looks the key up (its slot, < 0: not
+// registered); `strict` selects dalek's verify_strict rule (a header
+// signature, every message job), `cert` is the status word the job reports
+// to.  job_message then turns the id into the signed message.
+COA_DEV int job_load(const CertArgs& a, uint32_t job, bool& strict, uint32_t& cert, uint32_t* pk, uint32_t* rw,
+                     uint32_t* sw, uint32_t* msg) {
   const bool hdr = job < a.nc;
   const uint32_t vi = job - a.nc;
   const uint32_t c = hdr ? job : vote_cert(a.voff, a.nc, vi);
   cert = c;
+  strict = hdr;
   const uint32_t* sig = sel_ptr(hdr, a.hsigs + (uint64_t)c * 16, a.vsigs + (uint64_t)vi * 16);
-  uint32_t pk[8], rw[8], sw[8], msg[8];
   load8(pk, sel_ptr(hdr, a.origins + (uint64_t)c * 8, a.vpks + (uint64_t)vi * 8));
   load8(rw, sig);
   load8(sw, sig + 8);
   load8(msg, a.ids + (uint64_t)c * 8);
+  return key_lookup(a.keys, a.nk, pk);
+}
+COA_DEV void job_message(const CertArgs& a, bool hdr, uint32_t c, uint32_t* msg) {
+  if (!hdr && a.cdig) {  // Certificate::digest from the prologue kernel
+    load8(msg, a.cdig + (uint64_t)c * 8);
+  } else if (!hdr) {  // Certificate::digest = SHA-512(id || round u64 LE || origin)[..32]
+    round_origin_digest(msg, a.rounds[c], a.origins + (uint64_t)c * 8);
+  }
+}
+// A message job (k_msg_verify): always strict; the message is the id
+// (headers) or Vote::digest hashed here (votes).
+COA_DEV int job_load(const MsgArgs& a, uint32_t job, bool& strict, uint32_t& cert, uint32_t* pk, uint32_t* rw,
+                     uint32_t* sw, uint32_t* msg) {
+  cert = job;
+  strict = true;
+  const uint32_t* sig = a.sigs + (uint64_t)job * 16;
+  load8(pk, a.authors + (uint64_t)job * 8);
+  load8(rw, sig);
+  load8(sw, sig + 8);
+  load8(msg, a.ids + (uint64_t)job * 8);
+  return key_lookup(a.keys, a.nk, pk);
+}
+COA_DEV void job_message(const MsgArgs& a, bool, uint32_t job, uint32_t* msg) {
+  if (a.rounds) round_origin_digest(msg, a.rounds[job], a.origins + (uint64_t)job * 8);
+}
+
+// Phase A of one signature job, shared by the certificate and the message
+// kernels (A: CertArgs or MsgArgs, which name the key tables alike).
+template <class A>
+COA_DEV void job_comb(const A& a, uint32_t job, ge_p3& P, uint32_t& pre, uint32_t& cert) {
+  bool strict;
+  uint32_t pk[8], rw[8], sw[8], msg[8];
+  const int slot = job_load(a, job, strict, cert, pk, rw, sw, msg);
   ge_p3_identity(P);
-  const int slot = key_lookup(a.keys, a.nk, pk);
   if (slot < 0) {
     pre = PRE_UNCACHED;
     return;
   }
+  job_message(a, strict, cert, msg);
   uint64_t st[8];
   uint32_t h[16];
-  if (!hdr && a.cdig) {  // Certificate::digest from the prologue kernel
-    load8(msg, a.cdig + (uint64_t)c * 8);
-  } else if (!hdr) {  // Certificate::digest = SHA-512(id || round u64 LE || origin)[..32]
-    uint32_t in[18];
-    const uint64_t rd = a.rounds[c];
-#pragma unroll
-    for (int i = 0; i < 8; i++) in[i] = msg[i];
-    in[8] = (uint32_t)rd;
-    in[9] = (uint32_t)(rd >> 32);
-    load8(in + 10, a.origins + (uint64_t)c * 8);
-    coa_sha::hash_words<18>(st, in);
-    coa_sha::state_to_le_words(h, st);
-#pragma unroll
-    for (int i = 0; i < 8; i++) msg[i] = h[i];
-  }
   {  // k = SHA-512(R || A || M) mod l
     uint32_t in[24];
 #pragma unroll
@@ -207,7 +248,7 @@ COA_DEV void job_comb(const CertArgs& a, uint32_t job, ge_p3& P, uint32_t& pre, 
   const uint32_t kf = a.kflags[slot];
   pre = (sc_is_canonical(sw) ? 0u : PRE_S) | ((kf & COA_KEY_DECOMPRESSES) ? 0u : PRE_A) |
         ((kf & COA_KEY_SMALL_ORDER) ? PRE_SMALL_A : 0u) | ((kf & COA_KEY_TORSION_FREE) ? 0u : PRE_TORSION) |
-        (hdr ? PRE_HDR : 0u);
+        (strict ? PRE_HDR : 0u);
   // terms t < 32: B-comb bytes of s; t >= 32: key-comb bytes of k (signed
   // radix-256 digits = bytes of x + 0x80..80)
   uint32_t sd[8], kd[8];
@@ -254,12 +295,8 @@ COA_DEV void job_comb(const CertArgs& a, uint32_t job, ge_p3& P, uint32_t& pre, 
 // `P == decompress(R)` holds iff y_P == y_R (mod p; R's y is read as 255 bits,
 // y >= p meaning y - p) and, unless x_P == 0, x_P's sign equals R's sign bit:
 // when y_P == y_R the point P itself proves that R decompresses (to +-x_P).
-COA_DEV uint32_t job_verdict(const CertArgs& a, uint32_t job, uint32_t pre, const fe& x, const fe& y) {
-  if (pre & (PRE_NONE | PRE_UNCACHED)) return (pre & PRE_UNCACHED) ? COA_CST_UNCACHED : 0u;
+COA_DEV uint32_t sig_verdict(uint32_t pre, const uint32_t* rw, const fe& x, const fe& y) {
   const bool hdr = (pre & PRE_HDR) != 0;
-  const uint32_t* sig = sel_ptr(hdr, a.hsigs + (uint64_t)job * 16, a.vsigs + (uint64_t)(job - a.nc) * 16);
-  uint32_t rw[8];
-  load8(rw, sig);
   fe yr, xc, yc;
   fe_from_words(yr, rw);
   fe_canon(yr, yr);
@@ -290,6 +327,28 @@ COA_DEV uint32_t job_verdict(const CertArgs& a, uint32_t job, uint32_t pre, cons
   // weight-dependent verdict) -- the host's exact RLC path decides both
   return (eq && !(pre & PRE_TORSION)) ? 0u : COA_CST_VOTES_INCONCLUSIVE;
 }
+
+COA_DEV uint32_t job_verdict(const CertArgs& a, uint32_t job, uint32_t pre, const fe& x, const fe& y) {
+  if (pre & (PRE_NONE | PRE_UNCACHED)) return (pre & PRE_UNCACHED) ? COA_CST_UNCACHED : 0u;
+  const bool hdr = (pre & PRE_HDR) != 0;
+  const uint32_t* sig = sel_ptr(hdr, a.hsigs + (uint64_t)job * 16, a.vsigs + (uint64_t)(job - a.nc) * 16);
+  uint32_t rw[8];
+  load8(rw, sig);
+  return sig_verdict(pre, rw, x, y);
+}
+
+COA_DEV uint32_t job_verdict(const MsgArgs& a, uint32_t job, uint32_t pre, const fe& x, const fe& y) {
+  if (pre & (PRE_NONE | PRE_UNCACHED)) return (pre & PRE_UNCACHED) ? COA_CST_UNCACHED : 0u;
+  uint32_t rw[8];
+  load8(rw, a.sigs + (uint64_t)job * 16);
+  return sig_verdict(pre, rw, x, y);  // every job strict: COA_CST_BAD_HEADER_SIG or 0
+}
+
+// the job a chunk position stands for (certificates: key order when sorted)
+COA_DEV uint64_t job_at(const CertArgs& a, uint64_t pos, uint64_t jobs) {
+  return (a.perm && pos < jobs) ? a.perm[pos] : pos;
+}
+COA_DEV uint64_t job_at(const MsgArgs&, uint64_t pos, uint64_t) { return pos; }
 
 // Scratch slab of the throughput kernel: per job slot 9 uint4 rows, each row
 // lane-major (row r of slot q at uint4 index (q * 9 + r) * lanes + lane):
@@ -403,29 +462,31 @@ __global__ void __launch_bounds__(256) k_cert_digests(CertArgs a, uint32_t* __re
 // its R encoding.  Per vote: ~265/jobs field operations of inversion instead
 // of R's ~277-operation decompression.  pscr[0] is the chunk counter (zeroed
 // by the launcher); the slab holds jcap jobs per lane.
-template <int WAVES>
-__global__ void __launch_bounds__(256, WAVES) k_cert_verify(CertArgs a, uint32_t* __restrict__ pscr, uint32_t jcap) {
-  if (blockIdx.x < a.hdr_blocks) {  // header digest role, one lane per certificate
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.nc) return;
-    const uint64_t o0 = a.hdr_off[c], o1 = a.hdr_off[c + 1];
-    uint64_t st[8];
-    coa_sha::hash_mem(st, a.hdr_data + o0, o1 - o0);
-    uint32_t h[16], id[8];
-    coa_sha::state_to_le_words(h, st);
-    load8(id, a.ids + (uint64_t)c * 8);
-    bool same = true;
+// The header digest role of a leading block: lane c checks
+// SHA-512(Header::digest bytes of c)[..32] == ids[c].
+COA_DEV void header_digest_lane(const uint8_t* hdr_data, const uint64_t* hdr_off, const uint32_t* ids,
+                                uint32_t* status, uint32_t c) {
+  const uint64_t o0 = hdr_off[c], o1 = hdr_off[c + 1];
+  uint64_t st[8];
+  coa_sha::hash_mem(st, hdr_data + o0, o1 - o0);
+  uint32_t h[16], id[8];
+  coa_sha::state_to_le_words(h, st);
+  load8(id, ids + (uint64_t)c * 8);
+  bool same = true;
 #pragma unroll
-    for (int i = 0; i < 8; i++) same = same && h[i] == id[i];
-    if (!same) atomicOr(a.status + c, COA_CST_BAD_HEADER_ID);
-    return;
-  }
+  for (int i = 0; i < 8; i++) same = same && h[i] == id[i];
+  if (!same) atomicOr(status + c, COA_CST_BAD_HEADER_ID);
+}
+
+// The signature waves of a throughput grid (blocks from a.hdr_blocks on)
+// over `jobs` jobs of A (CertArgs or MsgArgs: job_at, job_comb, job_verdict).
+template <class A>
+COA_DEV void tp_signature_waves(const A& a, uint32_t* __restrict__ pscr, uint32_t jcap, uint64_t jobs) {
   const uint64_t lanes = (uint64_t)(gridDim.x - a.hdr_blocks) * blockDim.x;
   const uint64_t lane = (uint64_t)(blockIdx.x - a.hdr_blocks) * blockDim.x + threadIdx.x;
   const uint32_t sub = threadIdx.x & 63;
   uint32_t* ctr = pscr;
   uint32_t* slab = pscr + 64;
-  const uint64_t jobs = (uint64_t)a.nc + a.nv;
   const uint32_t chunks = (uint32_t)((jobs + 63) / 64);
   int nj = 0;  // this wave's chunks (the same for all its lanes)
   fe zp;       // running prefix product of the Z's
@@ -436,8 +497,7 @@ __global__ void __launch_bounds__(256, WAVES) k_cert_verify(CertArgs a, uint32_t
     if (sub == 0) chunk = atomicAdd(ctr, 1u);
     chunk = __builtin_amdgcn_readfirstlane(__shfl(chunk, 0));
     if (chunk >= chunks) break;
-    uint64_t job = (uint64_t)chunk * 64 + sub;
-    if (a.perm && job < jobs) job = a.perm[job];  // key order (k_job_count, k_job_place)
+    const uint64_t job = job_at(a, (uint64_t)chunk * 64 + sub, jobs);  // key order (k_job_count, k_job_place)
     ge_p3 P;
     uint32_t pre = PRE_NONE, cert = 0;
     if (job < jobs) job_comb(a, (uint32_t)job, P, pre, cert);
@@ -475,6 +535,34 @@ __global__ void __launch_bounds__(256, WAVES) k_cert_verify(CertArgs a, uint32_t
     const uint32_t bits = job_verdict(a, m.z, m.x, x, y);
     if (bits) atomicOr(a.status + m.y, bits);
   }
+}
+
+template <int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_cert_verify(CertArgs a, uint32_t* __restrict__ pscr, uint32_t jcap) {
+  if (blockIdx.x < a.hdr_blocks) {  // header digest role, one lane per certificate
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.nc) return;
+    header_digest_lane(a.hdr_data, a.hdr_off, a.ids, a.status, c);
+    return;
+  }
+  tp_signature_waves(a, pscr, jcap, (uint64_t)a.nc + a.nv);
+}
+
+// Header::verify / Vote::verify crypto of many messages: the throughput
+// design above with one strict job per message (MsgArgs, coa_committee.h).
+// Headers: the leading blocks check the Header::digest bytes against ids[i]
+// (bit 1) beside the signature waves (bit 2).  Votes: no leading blocks; each
+// job hashes Vote::digest itself.  A strict verdict depends on no weights,
+// so nothing is ever inconclusive: an unregistered author sets
+// COA_CST_UNCACHED and nothing else is decided for that job.
+template <int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_msg_verify(MsgArgs a, uint32_t* __restrict__ pscr, uint32_t jcap) {
+  if (blockIdx.x < a.hdr_blocks) {  // header digest role, one lane per header
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < a.n) header_digest_lane(a.hdr_data, a.hdr_off, a.ids, a.status, c);
+    return;
+  }
+  tp_signature_waves(a, pscr, jcap, (uint64_t)a.n);
 }
 
 // ---------------------------------------------------------------------------
@@ -1039,6 +1127,30 @@ hipError_t coa_launch_cert_verify(CertArgs a, int lanes_per_sig, uint32_t* pscr,
                        cert_tp_jcap(jobs, lanes));
   else
     hipLaunchKernelGGL(k_cert_verify<2>, dim3((uint32_t)(a.hdr_blocks + lanes / 256)), dim3(256), 0, s, a, pscr,
+                       cert_tp_jcap(jobs, lanes));
+  return hipGetLastError();
+}
+
+// Message scratch: [0, 256) chunk counter | slab (lanes x jcap jobs).
+size_t coa_msg_scratch_bytes(uint64_t n) {
+  const uint64_t jobs = n ? n : 1;
+  return 256 + cert_slab_bytes(jobs, cert_tp_lanes(jobs));
+}
+
+// The same grid as the certificates' (cert_tp_lanes, COA_CERT_WAVES); no
+// key-order sort.
+hipError_t coa_launch_msg_verify(MsgArgs a, uint32_t* pscr, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  a.hdr_blocks = a.hdr_data ? (a.n + 255) / 256 : 0;
+  const uint64_t jobs = a.n;
+  const uint64_t lanes = cert_tp_lanes(jobs);
+  hipError_t e = hipMemsetAsync(pscr, 0, 4, s);  // the chunk counter
+  if (e != hipSuccess) return e;
+  if (cert_tp_waves() == 3)
+    hipLaunchKernelGGL(k_msg_verify<3>, dim3((uint32_t)(a.hdr_blocks + lanes / 256)), dim3(256), 0, s, a, pscr,
+                       cert_tp_jcap(jobs, lanes));
+  else
+    hipLaunchKernelGGL(k_msg_verify<2>, dim3((uint32_t)(a.hdr_blocks + lanes / 256)), dim3(256), 0, s, a, pscr,
                        cert_tp_jcap(jobs, lanes));
   return hipGetLastError();
 }

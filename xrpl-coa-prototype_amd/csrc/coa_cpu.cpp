@@ -793,4 +793,47 @@ int coa_cpu_certificate_verify_many(const uint8_t* header_data, const uint64_t* 
                                            vote_sigs, vote_offsets, n, zs.data(), status_out, nthreads);
 }
 
+// Header::verify crypto (primary/src/messages.rs:49-51,64-66): the digest
+// check and verify_strict(header.id, author)
+int coa_cpu_header_verify_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                               const uint8_t* authors, const uint8_t* sigs, size_t n, uint8_t* status_out,
+                               int nthreads) {
+  if (n == 0) return COA_OK;
+  if (!header_offsets || !ids || !authors || !sigs || !status_out) return COA_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (header_offsets[i + 1] < header_offsets[i]) return COA_EINVAL;
+  if (header_offsets[n] > header_offsets[0] && !header_data) return COA_EINVAL;
+  ensure_consts();
+  parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) {
+      uint8_t bits = 0, h[64];
+      sha512(header_data + header_offsets[i], (size_t)(header_offsets[i + 1] - header_offsets[i]), h);
+      if (std::memcmp(h, ids + 32 * i, 32) != 0) bits |= COA_CERT_BAD_HEADER_ID;
+      if (verify_strict_one(ids + 32 * i, 32, authors + 32 * i, sigs + 64 * i)) bits |= COA_CERT_BAD_HEADER_SIG;
+      status_out[i] = bits;
+    }
+  });
+  return COA_OK;
+}
+
+// Vote::verify crypto (primary/src/messages.rs:139-153): verify_strict of
+// Vote::digest = SHA-512(id || round LE || origin)[..32] under vote.author
+int coa_cpu_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                             const uint8_t* sigs, size_t n, uint8_t* verdicts_out, int nthreads) {
+  if (n == 0) return COA_OK;
+  if (!ids || !rounds || !origins || !authors || !sigs || !verdicts_out) return COA_EINVAL;
+  ensure_consts();
+  parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; i++) {
+      uint8_t m[72], h[64];
+      std::memcpy(m, ids + 32 * i, 32);
+      for (int b = 0; b < 8; b++) m[32 + b] = (uint8_t)(rounds[i] >> (8 * b));
+      std::memcpy(m + 40, origins + 32 * i, 32);
+      sha512(m, 72, h);
+      verdicts_out[i] = (uint8_t)verify_strict_one(h, 32, authors + 32 * i, sigs + 64 * i);
+    }
+  });
+  return COA_OK;
+}
+
 }  // extern "C"

@@ -1711,6 +1711,167 @@ int certificates_impl(const CertIn& in, size_t n, uint64_t rng_seed, uint8_t* st
   return COA_OK;
 }
 
+// ------------------------------------------------------------------------
+// Header::verify / Vote::verify crypto for many messages (k_msg_verify).  A
+// shard [lo, hi) is packed into the context's pinned staging and copied with
+// ONE H2D; the raw status words come back with one D2H.
+struct MsgIn {
+  const uint8_t* hdr_data;  // headers only
+  const uint64_t* hdr_off;  // headers only
+  const uint8_t* ids;
+  const uint64_t* rounds;   // votes only
+  const uint8_t* origins;   // votes only
+  const uint8_t* authors;
+  const uint8_t* sigs;
+  bool votes;
+};
+
+struct MsgPack {
+  size_t status, ids, authors, sigs, rounds, origins, hoff, hdata, total;
+};
+MsgPack msg_layout(size_t n, bool votes, size_t hbytes) {
+  MsgPack p{};
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes, 256);
+    return at;
+  };
+  p.status = take(n * 4);
+  p.ids = take(n * 32);
+  p.authors = take(n * 32);
+  p.sigs = take(n * 64);
+  if (votes) {
+    p.rounds = take(n * 8);
+    p.origins = take(n * 32);
+  } else {
+    p.hoff = take((n + 1) * 8);
+    p.hdata = take(hbytes + 16);
+  }
+  p.total = o;
+  return p;
+}
+
+// the key tables of generation ks and context d's fixed-base combs
+void msg_key_args(MsgArgs& a, Dev& d, const KeySet& ks) {
+  a.keys = ks.ckeys.as<uint32_t>();
+  a.kflags = ks.kflags.as<uint32_t>();
+  a.ktabs = ks.ktabs.as<uint32_t>();
+  a.nk = ks.nkeys;
+  a.comb = d.comb;
+  a.wcomb = wcomb_of(d);
+  a.kwtabs = (ks.kwide && !env_is("COA_KEY_WCOMB", "0")) ? ks.kwtabs.as<uint32_t>() : nullptr;
+  a.kw20 = ks.kw20 ? 1u : 0u;
+}
+
+// Messages [lo, hi) on one context (its lock held): raw status words out.
+int msg_shard(Dev& d, const MsgIn& in, size_t lo, size_t hi, uint32_t* raw) {
+  const size_t n = hi - lo;
+  const uint64_t h0 = in.votes ? 0 : in.hdr_off[lo], hb = in.votes ? 0 : in.hdr_off[hi] - h0;
+  const MsgPack p = msg_layout(n, in.votes, hb);
+  HIP_TRY(d.pin.ensure(p.total));
+  HIP_TRY(d.cert.ensure(p.total));
+  HIP_TRY(d.cscr.ensure(coa_msg_scratch_bytes(n)));
+  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
+  std::memset(h + p.status, 0, n * 4);
+  std::vector<CopyPool::Seg> segs = {{h + p.ids, in.ids + lo * 32, n * 32},
+                                     {h + p.authors, in.authors + lo * 32, n * 32},
+                                     {h + p.sigs, in.sigs + lo * 64, n * 64}};
+  if (in.votes) {
+    segs.push_back({h + p.rounds, in.rounds + lo, n * 8});
+    segs.push_back({h + p.origins, in.origins + lo * 32, n * 32});
+  } else {
+    uint64_t* ho = reinterpret_cast<uint64_t*>(h + p.hoff);
+    for (size_t i = 0; i <= n; i++) ho[i] = in.hdr_off[lo + i] - h0;
+    if (hb) segs.push_back({h + p.hdata, in.hdr_data + h0, hb});
+  }
+  CopyPool::get().copy(segs);
+  hipStream_t s = d.stream;
+  uint8_t* base = d.cert.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(base, h, p.total, hipMemcpyHostToDevice, s));
+  const KeySetP ks = keys_now(d);  // held until the status words are in
+  MsgArgs a{};
+  a.ids = reinterpret_cast<const uint32_t*>(base + p.ids);
+  a.authors = reinterpret_cast<const uint32_t*>(base + p.authors);
+  a.sigs = reinterpret_cast<const uint32_t*>(base + p.sigs);
+  if (in.votes) {
+    a.rounds = reinterpret_cast<const uint64_t*>(base + p.rounds);
+    a.origins = reinterpret_cast<const uint32_t*>(base + p.origins);
+  } else {
+    a.hdr_data = base + p.hdata;
+    a.hdr_off = reinterpret_cast<const uint64_t*>(base + p.hoff);
+  }
+  a.n = (uint32_t)n;
+  msg_key_args(a, d, *ks);
+  a.status = reinterpret_cast<uint32_t*>(base + p.status);
+  HIP_TRY(coa_launch_msg_verify(a, d.cscr.as<uint32_t>(), s));
+  HIP_TRY(hipMemcpyAsync(h + p.status, base + p.status, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(raw + lo, h + p.status, n * 4);
+  return COA_OK;
+}
+
+// Raw words of all n messages, then the exact re-decision of the items whose
+// author is not registered through the uncached path: verify_strict over the
+// id (headers) or Vote::digest (votes).  A header's digest bit does not use
+// the cache and stands.
+int messages_impl(const MsgIn& in, size_t n, std::vector<uint32_t>& st) {
+  st.assign(n, 0);
+  int rc = for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int { return msg_shard(d, in, lo, hi, st.data()); });
+  if (rc != COA_OK) return rc;
+  std::vector<size_t> open;
+  for (size_t i = 0; i < n; i++)
+    if (st[i] & COA_CST_UNCACHED) open.push_back(i);
+  if (open.empty()) return COA_OK;
+  const size_t m = open.size();
+  std::vector<uint8_t> msgs(m * 32), pks(m * 32), sigs(m * 64), v(m);
+  for (size_t j = 0; j < m; j++) {
+    std::memcpy(&pks[j * 32], in.authors + open[j] * 32, 32);
+    std::memcpy(&sigs[j * 64], in.sigs + open[j] * 64, 64);
+  }
+  if (in.votes) {  // Vote::digest inputs: id || round LE || origin (72 B)
+    std::vector<uint8_t> vin(m * 72);
+    std::vector<uint64_t> off(m + 1);
+    for (size_t j = 0; j < m; j++) {
+      const size_t i = open[j];
+      std::memcpy(&vin[j * 72], in.ids + i * 32, 32);
+      for (int b = 0; b < 8; b++) vin[j * 72 + 32 + b] = (uint8_t)(in.rounds[i] >> (8 * b));
+      std::memcpy(&vin[j * 72 + 40], in.origins + i * 32, 32);
+      off[j] = j * 72;
+    }
+    off[m] = m * 72;
+    rc = coa_sha512_trunc32_many(vin.data(), off.data(), m, msgs.data());
+    if (rc != COA_OK) return rc;
+  } else {
+    for (size_t j = 0; j < m; j++) std::memcpy(&msgs[j * 32], in.ids + open[j] * 32, 32);
+  }
+  rc = coa_ed25519_verify_strict_many(msgs.data(), 32, pks.data(), sigs.data(), m, v.data());
+  if (rc != COA_OK) return rc;
+  for (size_t j = 0; j < m; j++)
+    st[open[j]] = (st[open[j]] & COA_CST_BAD_HEADER_ID) | (v[j] ? COA_CST_BAD_HEADER_SIG : 0u);
+  return COA_OK;
+}
+
+// Device-resident form of either shape (a.status zeroed here).
+int messages_device(int device, MsgArgs a, void* workspace, void* stream) {
+  Dev* d = dev_by_id(device);
+  if (!d) return fail(COA_EINVAL, "device not opened by coa_init");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  const KeySetP ks = keys_now(*d);  // pinned (the queue) or current
+  msg_key_args(a, *d, *ks);
+  HIP_TRY(hipMemsetAsync(a.status, 0, (size_t)a.n * 4, s));
+  if (workspace) {
+    HIP_TRY(coa_launch_msg_verify(a, static_cast<uint32_t*>(workspace), s));
+    return trail_keys(*d, ks, s);
+  }
+  std::lock_guard<std::mutex> l(d->mu);
+  HIP_TRY(d->cscr.ensure(coa_msg_scratch_bytes(a.n)));
+  HIP_TRY(coa_launch_msg_verify(a, d->cscr.as<uint32_t>(), s));
+  HIP_TRY(hipStreamSynchronize(s));  // engine-owned workspace: drain before release
+  return COA_OK;
+}
+
 int sign_enqueue(Dev& d, const uint8_t* d_seeds, const uint8_t* d_msgs, size_t msg_len, size_t n, uint8_t* d_pks,
                  uint8_t* d_sigs, hipStream_t s) {
   HIP_TRY(d.aux.ensure(n * 64 + 64));
@@ -2580,6 +2741,81 @@ int coa_certificate_verify_many_device_order(int device, const uint8_t* d_header
   HIP_TRY(coa_launch_cert_verify(a, lanes, d->cscr.as<uint32_t>(), s));
   HIP_TRY(hipStreamSynchronize(s));  // engine-owned workspace: drain before release
   return COA_OK;
+}
+
+int coa_header_verify_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                           const uint8_t* authors, const uint8_t* sigs, size_t n, uint8_t* status_out) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!header_offsets || !ids || !authors || !sigs || !status_out) return fail(COA_EINVAL, "null argument");
+  for (size_t i = 0; i < n; i++)
+    if (header_offsets[i + 1] < header_offsets[i]) return fail(COA_EINVAL, "offsets not monotone");
+  if (header_offsets[n] > header_offsets[0] && !header_data) return fail(COA_EINVAL, "null header data");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  const MsgIn in{header_data, header_offsets, ids, nullptr, nullptr, authors, sigs, false};
+  std::vector<uint32_t> st;
+  rc = messages_impl(in, n, st);
+  if (rc != COA_OK) return rc;
+  for (size_t i = 0; i < n; i++) status_out[i] = (uint8_t)(st[i] & 3u);
+  return COA_OK;
+}
+
+int coa_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                         const uint8_t* sigs, size_t n, uint8_t* verdicts_out) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!ids || !rounds || !origins || !authors || !sigs || !verdicts_out) return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  const MsgIn in{nullptr, nullptr, ids, rounds, origins, authors, sigs, true};
+  std::vector<uint32_t> st;
+  rc = messages_impl(in, n, st);
+  if (rc != COA_OK) return rc;
+  for (size_t i = 0; i < n; i++) verdicts_out[i] = (st[i] & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
+  return COA_OK;
+}
+
+size_t coa_message_workspace_bytes(size_t n) { return coa_msg_scratch_bytes(n); }
+
+int coa_header_verify_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                  const uint8_t* d_ids, const uint8_t* d_authors, const uint8_t* d_sigs, size_t n,
+                                  uint32_t* d_status, void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!d_header_data || !d_header_offsets || !d_ids || !d_authors || !d_sigs || !d_status)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  MsgArgs a{};
+  a.hdr_data = d_header_data;
+  a.hdr_off = d_header_offsets;
+  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
+  a.authors = reinterpret_cast<const uint32_t*>(d_authors);
+  a.sigs = reinterpret_cast<const uint32_t*>(d_sigs);
+  a.n = (uint32_t)n;
+  a.status = d_status;
+  return messages_device(device, a, workspace, stream);
+}
+
+int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
+                                const uint8_t* d_authors, const uint8_t* d_sigs, size_t n, uint32_t* d_status,
+                                void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!d_ids || !d_rounds || !d_origins || !d_authors || !d_sigs || !d_status)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  MsgArgs a{};
+  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
+  a.rounds = d_rounds;
+  a.origins = reinterpret_cast<const uint32_t*>(d_origins);
+  a.authors = reinterpret_cast<const uint32_t*>(d_authors);
+  a.sigs = reinterpret_cast<const uint32_t*>(d_sigs);
+  a.n = (uint32_t)n;
+  a.status = d_status;
+  return messages_device(device, a, workspace, stream);
 }
 
 }  // extern "C"
