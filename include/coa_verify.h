@@ -443,6 +443,33 @@ int coa_queue_submit_certificate_borrowed(coa_queue* q, const uint8_t* header_da
 /* Worker batch digests (worker/src/processor.rs:38, Processor::spawn): the
  * callback receives the 32-byte Digest (n = 32). */
 int coa_queue_submit_digest(coa_queue* q, const uint8_t* data, size_t len, coa_verdict_cb cb, void* user);
+/* Whole headers: Header::verify's crypto (primary/src/messages.rs:49-51, the
+ * id check, and 64-66, the author's signature over the id), with
+ * coa_header_verify_many's semantics.  The callback receives one status byte
+ * of COA_CERT_BAD_HEADER_ID | COA_CERT_BAD_HEADER_SIG bits (0 = both Ok).
+ * Inputs are copied at submission. */
+int coa_queue_submit_header(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
+                            const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user);
+/* Whole votes: Vote::verify's crypto (primary/src/messages.rs:145-153,
+ * Vote::digest, and 139-141, the author's signature over it), with
+ * coa_vote_verify_many's semantics: Vote::digest is hashed on the device.  The
+ * callback receives one verdict byte, 0 Ok / 1 Err. */
+int coa_queue_submit_vote(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
+                          const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user);
+/* Both kinds live on the verdict lane, count one item each towards max_batch
+ * and one signature each in coa_queue_stats / coa_queue_metrics, and run on
+ * the registered committee's key combs: a window of at most
+ * COA_QUEUE_MSG_LAT_MAX messages (read at coa_queue_create) takes the latency
+ * kernel (one workgroup per message; alone in its window and at most 64, its
+ * verdict words are published to page-locked memory, no copy back), a larger
+ * one the throughput kernels of coa_header_verify_many_device /
+ * coa_vote_verify_many_device.  A message whose author is not registered is
+ * decided by the resolver thread through the uncached path, so the answer is
+ * dalek's verify_strict plus the digest check with any committee or none.
+ * No reference counterpart: requests and windows of each route since creation
+ * or the last coa_queue_metrics_reset (any pointer may be null). */
+int coa_queue_message_stats(coa_queue* q, uint64_t* headers, uint64_t* votes, uint64_t* latency_windows,
+                            uint64_t* throughput_windows);
 int coa_queue_flush(coa_queue* q);
 /* Window policy (no reference counterpart): with windows_in_flight = k > 0 a
  * window also closes at once while fewer than k windows are in flight, so a
@@ -525,6 +552,8 @@ typedef struct {
 #define COA_QUEUE_KIND_BATCHES 2u
 #define COA_QUEUE_KIND_CERTIFICATES 4u
 #define COA_QUEUE_KIND_DIGESTS 8u
+#define COA_QUEUE_KIND_HEADERS 16u
+#define COA_QUEUE_KIND_VOTES 32u
 /* COA_QUEUE_STREAMS=plain|cumask|priority (read at the first launch): plain
  * streams share the process's GPU_MAX_HW_QUEUES hardware queues (HIP's
  * default 4) with every other stream of the process; CU-masked streams (all

@@ -233,6 +233,12 @@ extern "C" {
                                         cb: CoaVerdictCb, user: *mut c_void) -> c_int;
     pub fn coa_queue_submit_digest(q: *mut CoaQueue, data: *const u8, len: usize, cb: CoaVerdictCb,
                                    user: *mut c_void) -> c_int;
+    pub fn coa_queue_submit_header(q: *mut CoaQueue, header_data: *const u8, header_len: usize, id: *const u8,
+                                   author: *const u8, sig: *const u8, cb: CoaVerdictCb, user: *mut c_void) -> c_int;
+    pub fn coa_queue_submit_vote(q: *mut CoaQueue, id: *const u8, round: u64, origin: *const u8, author: *const u8,
+                                 sig: *const u8, cb: CoaVerdictCb, user: *mut c_void) -> c_int;
+    pub fn coa_queue_message_stats(q: *mut CoaQueue, headers: *mut u64, votes: *mut u64, latency_windows: *mut u64,
+                                   throughput_windows: *mut u64) -> c_int;
     pub fn coa_queue_flush(q: *mut CoaQueue) -> c_int;
     pub fn coa_queue_set_idle_launch(q: *mut CoaQueue, windows_in_flight: u32) -> c_int;
     pub fn coa_queue_stats(q: *mut CoaQueue, launches: *mut u64, items: *mut u64, groups: *mut u64) -> c_int;

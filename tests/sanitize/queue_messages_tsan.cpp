@@ -1,0 +1,322 @@
+// Sanitizer run of the aggregation queue (xrpl-coa-prototype_amd/csrc/
+// coa_queue.cpp) with all six request kinds: bare signatures, vote batches,
+// certificates, digests and -- what this program is about -- whole headers
+// (coa_queue_submit_header) and whole votes (coa_queue_submit_vote).  The
+// launch backend is a deterministic stub of its own (no GPU, no HIP): every
+// verdict is a pure function of the request's bytes, so each callback is
+// checked against the request it answers.  As the HIP backend leaves the
+// messages of unregistered authors to the resolver, the stub defers every
+// message whose author[5] is odd (a deferred header keeps its digest bit from
+// the launch; the resolver adds the signature bit), so both the window's and
+// the resolver's answers are exercised for both kinds.
+//
+// Build (tests/test_queue_messages.py): clang++ -fsanitize=thread, and g++
+// -fsanitize=address,undefined, coa_queue.cpp queue_messages_tsan.cpp.
+// usage: queue_messages_tsan <producers> <requests per producer>
+//        [fail every k-th launch] [1: every retry fails too]
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <random>
+#include <thread>
+#include <vector>
+
+#include "coa_queue.h"
+#include "coa_verify.h"
+
+static std::atomic<long> g_engine_calls{0}, g_injected{0}, g_resolver_passes{0}, g_resolved{0};
+static std::atomic<long> g_lat_windows{0}, g_tp_windows{0};
+static unsigned long g_fault_every = 0;
+static bool g_fault_all = false;
+static uint8_t v_single(const uint8_t* msg, const uint8_t* sig) { return (uint8_t)((msg[0] ^ sig[0]) & 1u); }
+static uint8_t v_group(const uint8_t* msg, size_t nvotes) { return (uint8_t)((msg[1] + nvotes) & 1u); }
+static uint8_t v_cert(const uint8_t* id, size_t nvotes) { return (uint8_t)((id[2] + nvotes) & 7u); }
+static uint8_t v_digest(const uint8_t* data, size_t len, int j) {
+  return (uint8_t)((len ? data[0] : 0xa5) + 7 * j + (uint8_t)len);
+}
+// a header's two bits: its bytes against its id, its signature against its id
+static uint8_t v_header_id(const uint8_t* hdr, size_t len, const uint8_t* id) {
+  return (uint8_t)(((len ? hdr[len - 1] : 0x5a) ^ id[0] ^ (uint8_t)len) & 1u);
+}
+static uint8_t v_header_sig(const uint8_t* id, const uint8_t* author, const uint8_t* sig) {
+  return (uint8_t)(((id[1] ^ author[1] ^ sig[63]) & 1u) << 1);
+}
+static uint8_t v_vote(const uint8_t* id, uint64_t round, const uint8_t* origin, const uint8_t* author,
+                      const uint8_t* sig) {
+  return (uint8_t)((id[4] + (uint8_t)round + (uint8_t)(round >> 40) + origin[2] + author[3] + sig[7]) & 1u);
+}
+static bool defers(const uint8_t* author) { return (author[5] & 1u) != 0; }
+
+namespace {
+void run_launch(coa_q::Launch& L) {
+  for (coa_q::Window* wp : L.parts) {
+    coa_q::Window& w = *wp;
+    for (size_t i = 0; i < w.nv; i++) w.v_out[i] = v_single(&w.v_msgs[i * 32], &w.v_sigs[i * 64]);
+    w.g_defer = w.ng > 0;
+    for (size_t c = 0; c < w.nc; c++) {
+      if (w.c_refs[c].id[3] & 1u)
+        w.c_defer.push_back((uint32_t)c);
+      else
+        w.c_out[c] = v_cert(w.c_refs[c].id, w.c_refs[c].nv);
+    }
+    for (size_t i = 0; i < w.nd; i++)
+      for (int j = 0; j < 32; j++)
+        w.d_out[i * 32 + j] = v_digest(w.d_data.data() + w.d_offs[i], w.d_offs[i + 1] - w.d_offs[i], j);
+    // messages: headers as i, votes as nhd + j, ascending
+    for (size_t i = 0; i < w.nhd; i++) {
+      const uint8_t* id = &w.hd_ids[i * 32];
+      const uint8_t* author = &w.hd_authors[i * 32];
+      w.hd_out[i] = v_header_id(w.hd_data.data() + w.hd_offs[i], w.hd_offs[i + 1] - w.hd_offs[i], id);
+      if (defers(author))
+        w.m_defer.push_back((uint32_t)i);
+      else
+        w.hd_out[i] |= v_header_sig(id, author, &w.hd_sigs[i * 64]);
+    }
+    for (size_t i = 0; i < w.nvt; i++) {
+      const uint8_t* author = &w.vt_authors[i * 32];
+      if (defers(author))
+        w.m_defer.push_back((uint32_t)(w.nhd + i));
+      else
+        w.vt_out[i] = v_vote(&w.vt_ids[i * 32], w.vt_rounds[i], &w.vt_origins[i * 32], author, &w.vt_sigs[i * 64]);
+    }
+  }
+  if (L.nhd + L.nvt) {  // the route, as the HIP backend reports it
+    L.msg_route = L.nhd + L.nvt <= 8 ? coa_q::Launch::MSG_LATENCY : coa_q::Launch::MSG_THROUGHPUT;
+    (L.msg_route == coa_q::Launch::MSG_LATENCY ? g_lat_windows : g_tp_windows)++;
+  }
+  L.rc = COA_OK;
+}
+
+class StubBackend : public coa_q::Backend {
+ public:
+  int slots() const override { return 2; }
+  int devices() const override { return 2; }
+  void launch(coa_q::Launch& L) override {
+    std::unique_lock<std::mutex> l(m_);
+    const int k = (int)(next_++ % 2);
+    cv_.wait(l, [&] { return !busy_[k]; });
+    busy_[k] = true;
+    L.slot = k;
+    fail_[k] = g_fault_every && next_ % g_fault_every == 0;
+  }
+  bool wait_free_slot() override {
+    std::unique_lock<std::mutex> l(m_);
+    if (!busy_[0] || !busy_[1]) return false;
+    cv_.wait(l, [&] { return !busy_[0] || !busy_[1]; });
+    return true;
+  }
+  void complete(coa_q::Launch& L) override {
+    g_engine_calls++;
+    std::this_thread::sleep_for(std::chrono::microseconds(50));
+    bool failed;
+    {
+      std::lock_guard<std::mutex> l(m_);
+      failed = fail_[L.slot];
+    }
+    if (failed) {
+      g_injected++;
+      L.rc = COA_EHIP;  // outputs stay at their "failed" values
+    } else {
+      run_launch(L);
+    }
+    std::lock_guard<std::mutex> l(m_);
+    busy_[L.slot] = false;
+    cv_.notify_all();
+  }
+  void retry(coa_q::Launch& L, int attempt) override {
+    if (attempt < 1 || attempt > devices()) std::abort();
+    if (g_fault_all) {
+      L.rc = COA_EHIP;
+      return;
+    }
+    run_launch(L);
+  }
+  int resolve(const std::vector<coa_q::Window*>& ws) override {
+    g_resolver_passes++;
+    std::this_thread::sleep_for(std::chrono::microseconds(200));  // slower than a window: the rest must not wait
+    for (coa_q::Window* w : ws) {
+      for (uint32_t c : w->c_defer) {
+        w->c_out[c] = v_cert(w->c_refs[c].id, w->c_refs[c].nv);
+        g_resolved++;
+      }
+      for (uint32_t m : w->m_defer) {
+        if (m < w->nhd) {
+          w->hd_out[m] = (uint8_t)((w->hd_out[m] & 1u) |
+                                   v_header_sig(&w->hd_ids[m * 32], &w->hd_authors[m * 32], &w->hd_sigs[m * 64]));
+        } else {
+          const size_t i = m - w->nhd;
+          w->vt_out[i] = v_vote(&w->vt_ids[i * 32], w->vt_rounds[i], &w->vt_origins[i * 32], &w->vt_authors[i * 32],
+                                &w->vt_sigs[i * 64]);
+        }
+        g_resolved++;
+      }
+      if (w->g_defer)
+        for (size_t g = 0; g < w->ng; g++) {
+          w->g_out[g] = v_group(&w->g_msgs[g * 32], w->g_offs[g + 1] - w->g_offs[g]);
+          g_resolved++;
+        }
+    }
+    return COA_OK;
+  }
+
+ private:
+  std::mutex m_;
+  std::condition_variable cv_;
+  bool busy_[2] = {false, false};
+  bool fail_[2] = {false, false};
+  unsigned long next_ = 0;
+};
+}  // namespace
+
+coa_q::Backend* coa_q::make_backend(int) { return new StubBackend(); }
+
+// -------------------------------------------------------------- producers
+struct Req {
+  uint8_t expect[32];
+  size_t n_expect;
+  std::atomic<int> done{0};
+  std::atomic<int> bad{0};
+};
+
+static std::atomic<long> g_engine_errors{0};
+static void check_cb(void* user, int status, const uint8_t* verdicts, size_t n) {
+  Req* r = static_cast<Req*>(user);
+  if (status == COA_EHIP) {
+    g_engine_errors++;
+    if (!g_fault_all) r->bad++;
+  } else if (status != COA_OK || n != r->n_expect || std::memcmp(verdicts, r->expect, n) != 0) {
+    r->bad++;
+  }
+  r->done++;
+}
+
+int main(int argc, char** argv) {
+  const int producers = argc > 1 ? std::atoi(argv[1]) : 8;
+  const int per = argc > 2 ? std::atoi(argv[2]) : 400;
+  g_fault_every = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 0;
+  g_fault_all = argc > 4 && std::atoi(argv[4]) == 1;
+  coa_queue* q = coa_queue_create(64, 200);
+  std::vector<std::vector<Req>> reqs(producers);
+  for (auto& v : reqs) v = std::vector<Req>(per);
+  std::atomic<long> n_headers{0}, n_votes{0}, n_deferred_msgs{0};
+  std::vector<std::thread> th;
+  for (int p = 0; p < producers; p++) {
+    th.emplace_back([&, p] {
+      std::mt19937 rng(2000 + p);
+      for (int i = 0; i < per; i++) {
+        Req& r = reqs[p][i];
+        uint8_t a[32], b[64], c[32], d[32];
+        for (auto& x : a) x = (uint8_t)rng();
+        for (auto& x : b) x = (uint8_t)rng();
+        for (auto& x : c) x = (uint8_t)rng();
+        for (auto& x : d) x = (uint8_t)rng();
+        int rc = COA_OK;
+        r.n_expect = 1;
+        switch (rng() % 8) {
+          case 0:
+            r.expect[0] = v_single(a, b);
+            rc = coa_queue_submit_verify(q, a, c, b, check_cb, &r);
+            break;
+          case 1: {
+            const size_t nv = rng() % 5;
+            std::vector<uint8_t> pks(nv * 32 + 1, 1), sigs(nv * 64 + 1, 2);
+            r.expect[0] = v_group(a, nv);
+            rc = coa_queue_submit_batch(q, a, pks.data(), sigs.data(), nv, check_cb, &r);
+            break;
+          }
+          case 2: {
+            const size_t nv = rng() % 4;
+            std::vector<uint8_t> hdr(rng() % 100), pks(nv * 32 + 1, 3), sigs(nv * 64 + 1, 4);
+            r.expect[0] = v_cert(a, nv);
+            rc = coa_queue_submit_certificate(q, hdr.data(), hdr.size(), a, c, b, 9, pks.data(), sigs.data(), nv,
+                                              check_cb, &r);
+            break;
+          }
+          case 3: {
+            std::vector<uint8_t> data(rng() % 300);
+            for (auto& x : data) x = (uint8_t)rng();
+            r.n_expect = 32;
+            for (int j = 0; j < 32; j++) r.expect[j] = v_digest(data.data(), data.size(), j);
+            rc = coa_queue_submit_digest(q, data.data(), data.size(), check_cb, &r);
+            break;
+          }
+          case 4:
+          case 5: {  // a whole header (a = id, c = author, b = signature), lengths 0..4,099
+            std::vector<uint8_t> hdr(rng() % 8 == 0 ? rng() % 4100 : rng() % 200);
+            for (auto& x : hdr) x = (uint8_t)rng();
+            r.expect[0] = (uint8_t)(v_header_id(hdr.data(), hdr.size(), a) | v_header_sig(a, c, b));
+            n_headers++;
+            if (defers(c)) n_deferred_msgs++;
+            rc = coa_queue_submit_header(q, hdr.data(), hdr.size(), a, c, b, check_cb, &r);
+            break;
+          }
+          default: {  // a whole vote (a = id, d = origin, c = author, b = signature)
+            const uint64_t round = ((uint64_t)rng() << 32) | rng();
+            r.expect[0] = v_vote(a, round, d, c, b);
+            n_votes++;
+            if (defers(c)) n_deferred_msgs++;
+            rc = coa_queue_submit_vote(q, a, round, d, c, b, check_cb, &r);
+            break;
+          }
+        }
+        if (rc != COA_OK) r.bad++, r.done++;
+        if (rng() % 97 == 0) coa_queue_flush(q);  // flushes race with submissions and the worker
+        if (rng() % 53 == 0) {
+          uint64_t l, it, g, h, v, lw, tw;
+          coa_queue_stats(q, &l, &it, &g);
+          coa_queue_message_stats(q, &h, &v, &lw, &tw);
+          coa_queue_metrics_t mm;
+          coa_queue_metrics(q, &mm);
+        }
+      }
+    });
+  }
+  for (auto& t : th) t.join();
+  coa_queue_flush(q);
+  long done = 0, bad = 0;
+  for (auto& v : reqs)
+    for (auto& r : v) {
+      done += r.done.load();
+      bad += r.bad.load();
+    }
+  uint64_t launches = 0, items = 0, groups = 0, digests = 0, headers = 0, votes = 0, lat_w = 0, tp_w = 0;
+  coa_queue_stats(q, &launches, &items, &groups);
+  coa_queue_digest_count(q, &digests);
+  coa_queue_message_stats(q, &headers, &votes, &lat_w, &tp_w);
+  coa_queue_metrics_t m;
+  coa_queue_metrics(q, &m);
+  coa_queue_destroy(q);
+  const long total = (long)producers * per;
+  std::printf("queue messages: %ld/%ld answered, %ld wrong, %llu headers, %llu votes, %llu launches, injected %ld, "
+              "retried %llu, recovered %llu, failed %llu, engine errors %ld, deferred %llu in %llu passes, message "
+              "windows %llu latency %llu throughput\n",
+              done, total, bad, (unsigned long long)headers, (unsigned long long)votes, (unsigned long long)launches,
+              g_injected.load(), (unsigned long long)m.retried_windows, (unsigned long long)m.recovered_windows,
+              (unsigned long long)m.failed_windows, g_engine_errors.load(), (unsigned long long)m.deferred_requests,
+              (unsigned long long)m.resolver_passes, (unsigned long long)lat_w, (unsigned long long)tp_w);
+  const bool recovery_ok =
+      m.retried_windows == (uint64_t)g_injected.load() &&
+      (g_fault_all ? (m.recovered_windows == 0 && m.failed_windows == m.retried_windows &&
+                      (g_injected.load() == 0 || g_engine_errors.load() > 0))
+                   : (m.recovered_windows == m.retried_windows && m.failed_windows == 0 && g_engine_errors.load() == 0));
+  // every deferred request was answered by a resolver pass; without failed
+  // windows the deferred messages are at least the ones the producers counted
+  const bool defer_ok = m.deferred_requests == (uint64_t)g_resolved.load() &&
+                        m.resolver_passes == (uint64_t)g_resolver_passes.load() && m.deferred_requests > 0 &&
+                        (g_fault_all || m.deferred_requests >= (uint64_t)n_deferred_msgs.load());
+  // the message counters: every header and vote counted once, each also one
+  // signature, and the route windows are the ones the backend reported (a
+  // re-run window once, a window whose every attempt failed not at all)
+  const bool message_ok = headers == (uint64_t)n_headers.load() && votes == (uint64_t)n_votes.load() &&
+                          headers > 0 && votes > 0 && n_deferred_msgs.load() > 0 && lat_w + tp_w > 0 &&
+                          lat_w + tp_w <= m.windows && lat_w == (uint64_t)g_lat_windows.load() &&
+                          tp_w == (uint64_t)g_tp_windows.load();
+  const bool metrics_ok = m.requests == (uint64_t)total && m.signatures == items && items >= headers + votes &&
+                          m.windows == launches && recovery_ok && defer_ok && message_ok;
+  return (done == total && bad == 0 && items + groups + digests == (uint64_t)total && metrics_ok) ? 0 : 1;
+}

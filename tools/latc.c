@@ -389,3 +389,140 @@ int latc_stream_certificates(size_t max_batch, unsigned max_delay_us, int produc
   if (atomic_load(&answered) != (long)(n * (size_t)rounds)) atomic_fetch_add(&wrong, 1);
   return atomic_load(&wrong);
 }
+
+/* ------------------------------------------------------------------------
+ * Headers or votes through an existing queue from `producers` threads
+ * (tools/queue_message_ab.py): message k goes from thread k % producers,
+ * `rounds` passes over the n messages.
+ *   route 0  whole messages: coa_queue_submit_header / coa_queue_submit_vote
+ *   route 1  the route before those existed: the producer hashes on the host
+ *            (coa_cpu_sha512_many, one thread) -- Vote::digest for a vote; for
+ *            a header the id check SHA-512(header bytes)[..32] == id -- and
+ *            submits the bare triple with coa_queue_submit_verify
+ * rate_per_s > 0 paces the submissions (the i-th of a thread at t0 + i /
+ * its share of the rate; sleeping, so an idle queue sees idle producers), 0
+ * submits as fast as the threads go.  Expected answers: expect[k] = a header's
+ * status bits or a vote's verdict byte.  Returns the number of wrong, failed
+ * or missing answers; wall time to the last answer into *elapsed_s. */
+typedef struct {
+  const uint8_t* expect;
+  uint8_t id_bit; /* route 1, headers: the host's id check */
+  int header_bits; /* the answer is a verdict to be combined into status bits */
+  atomic_int* wrong;
+  atomic_long* answered;
+} MsgReq;
+
+typedef struct {
+  coa_queue* q;
+  int route, votes, p, producers, rounds;
+  double rate, t0_us;
+  size_t n;
+  const uint8_t *hdata, *ids, *origins, *authors, *sigs, *expect;
+  const uint64_t *hoff, *rounds_of;
+  atomic_int* wrong;
+  atomic_long* answered;
+} MsgJob;
+
+static void msg_cb(void* user, int status, const uint8_t* v, size_t n) {
+  MsgReq* r = (MsgReq*)user;
+  uint8_t got = (n == 1 && v) ? v[0] : 0xff;
+  if (r->header_bits) got = (uint8_t)(r->id_bit | (got ? 2 : 0));
+  if (status != COA_OK || n != 1 || got != r->expect[0]) atomic_fetch_add(r->wrong, 1);
+  atomic_fetch_add(r->answered, 1);
+  free(r);
+}
+
+static void* msg_thread(void* arg) {
+  MsgJob* j = (MsgJob*)arg;
+  size_t sent = 0;
+  for (int r = 0; r < j->rounds; r++)
+    for (size_t k = (size_t)j->p; k < j->n; k += (size_t)j->producers, sent++) {
+      if (j->rate > 0) {
+        const double due = j->t0_us + (double)sent * 1e6 / j->rate;
+        for (;;) {
+          const double left = due - now_us();
+          if (left <= 0) break;
+          if (left > 300.0) {
+            struct timespec ts = {0, (long)((left - 150.0) * 1e3)};
+            nanosleep(&ts, NULL);
+          }
+        }
+      }
+      MsgReq* m = (MsgReq*)malloc(sizeof(MsgReq));
+      m->expect = j->expect + k;
+      m->id_bit = 0;
+      m->header_bits = 0;
+      m->wrong = j->wrong;
+      m->answered = j->answered;
+      int rc;
+      if (j->route == 0 && j->votes) {
+        rc = coa_queue_submit_vote(j->q, j->ids + 32 * k, j->rounds_of[k], j->origins + 32 * k, j->authors + 32 * k,
+                                   j->sigs + 64 * k, msg_cb, m);
+      } else if (j->route == 0) {
+        rc = coa_queue_submit_header(j->q, j->hdata + j->hoff[k], j->hoff[k + 1] - j->hoff[k], j->ids + 32 * k,
+                                     j->authors + 32 * k, j->sigs + 64 * k, msg_cb, m);
+      } else if (j->votes) {
+        uint8_t in[72], dig[64];
+        const uint64_t off[2] = {0, 72};
+        memcpy(in, j->ids + 32 * k, 32);
+        for (int b = 0; b < 8; b++) in[32 + b] = (uint8_t)(j->rounds_of[k] >> (8 * b));
+        memcpy(in + 40, j->origins + 32 * k, 32);
+        rc = coa_cpu_sha512_many(in, off, 1, dig, 1);
+        if (rc == COA_OK) rc = coa_queue_submit_verify(j->q, dig, j->authors + 32 * k, j->sigs + 64 * k, msg_cb, m);
+      } else {
+        uint8_t dig[64];
+        const uint64_t off[2] = {0, j->hoff[k + 1] - j->hoff[k]};
+        rc = coa_cpu_sha512_many(j->hdata + j->hoff[k], off, 1, dig, 1);
+        m->header_bits = 1;
+        m->id_bit = memcmp(dig, j->ids + 32 * k, 32) != 0;
+        if (rc == COA_OK)
+          rc = coa_queue_submit_verify(j->q, j->ids + 32 * k, j->authors + 32 * k, j->sigs + 64 * k, msg_cb, m);
+      }
+      if (rc != COA_OK) {
+        atomic_fetch_add(j->wrong, 1);
+        atomic_fetch_add(j->answered, 1);
+        free(m);
+      }
+    }
+  return NULL;
+}
+
+int latc_queue_messages(coa_queue* q, int route, int votes, int producers, int rounds, double rate_per_s,
+                        const uint8_t* hdata, const uint64_t* hoff, const uint8_t* ids, const uint64_t* rounds_of,
+                        const uint8_t* origins, const uint8_t* authors, const uint8_t* sigs, size_t n,
+                        const uint8_t* expect, double* elapsed_s) {
+  if (!q || producers < 1 || producers > 64) return -1;
+  atomic_int wrong = 0;
+  atomic_long answered = 0;
+  MsgJob jobs[64];
+  pthread_t th[64];
+  const double t0 = now_us();
+  for (int p = 0; p < producers; p++) {
+    MsgJob* j = &jobs[p];
+    j->q = q;
+    j->route = route;
+    j->votes = votes;
+    j->p = p;
+    j->producers = producers;
+    j->rounds = rounds;
+    j->rate = rate_per_s / producers;
+    j->t0_us = t0;
+    j->n = n;
+    j->hdata = hdata;
+    j->hoff = hoff;
+    j->ids = ids;
+    j->rounds_of = rounds_of;
+    j->origins = origins;
+    j->authors = authors;
+    j->sigs = sigs;
+    j->expect = expect;
+    j->wrong = &wrong;
+    j->answered = &answered;
+  }
+  for (int p = 0; p < producers; p++) pthread_create(&th[p], NULL, msg_thread, &jobs[p]);
+  for (int p = 0; p < producers; p++) pthread_join(th[p], NULL);
+  coa_queue_flush(q);
+  *elapsed_s = (now_us() - t0) * 1e-6;
+  if (atomic_load(&answered) != (long)(n * (size_t)rounds)) atomic_fetch_add(&wrong, 1);
+  return atomic_load(&wrong);
+}

@@ -169,6 +169,9 @@ def lib():
         "coa_queue_submit_certificate_borrowed": ([vp, P8, sz, P8, P8, P8, ctypes.c_uint64, P8, P8, sz, VERDICT_CB,
                                                    vp], ctypes.c_int),
         "coa_queue_submit_digest": ([vp, P8, sz, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_submit_header": ([vp, P8, sz, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_submit_vote": ([vp, P8, ctypes.c_uint64, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_message_stats": ([vp, P64, P64, P64, P64], ctypes.c_int),
         "coa_queue_digest_count": ([vp, P64], ctypes.c_int),
         "coa_queue_flush": ([vp], ctypes.c_int),
         "coa_queue_set_idle_launch": ([vp, ctypes.c_uint32], ctypes.c_int),
@@ -776,6 +779,34 @@ def vote_verify_many_device(device, ids, rounds, origins, authors, sigs, status,
                                              _handle(device, stream)))
 
 
+class _MsgLatIn(ctypes.Structure):
+    """CoaMsgLatIn (csrc/coa_committee.h)."""
+    _fields_ = [("hdr_data", ctypes.c_void_p), ("hdr_off", ctypes.c_void_p), ("hids", ctypes.c_void_p),
+                ("hauthors", ctypes.c_void_p), ("hsigs", ctypes.c_void_p), ("nh", ctypes.c_uint64),
+                ("vids", ctypes.c_void_p), ("vrounds", ctypes.c_void_p), ("vorigins", ctypes.c_void_p),
+                ("vauthors", ctypes.c_void_p), ("vsigs", ctypes.c_void_p), ("nv", ctypes.c_uint64)]
+
+
+def message_lat_verify_device(device, headers, votes, status, stream=None):
+    """The message latency kernel (k_msg_verify_lat) on device-resident
+    tensors, through the engine's internal coa_msg_lat_verify_device (the entry
+    the aggregation queue uses; not part of include/coa_verify.h).  headers:
+    None or (hdata, hoff, ids, authors, sigs); votes: None or (ids, rounds,
+    origins, authors, sigs); status: uint32 tensor [nh + nv] of raw words, the
+    headers' first, as the throughput device forms write them."""
+    f = lib().coa_msg_lat_verify_device
+    f.argtypes = [ctypes.c_int, ctypes.POINTER(_MsgLatIn), ctypes.c_void_p, ctypes.c_void_p]
+    f.restype = ctypes.c_int
+    a = _MsgLatIn()
+    if headers is not None:
+        a.hdr_data, a.hdr_off, a.hids, a.hauthors, a.hsigs = [t.data_ptr() for t in headers]
+        a.nh = headers[2].shape[0]
+    if votes is not None:
+        a.vids, a.vrounds, a.vorigins, a.vauthors, a.vsigs = [t.data_ptr() for t in votes]
+        a.nv = votes[0].shape[0]
+    _check(f(device, ctypes.byref(a), status.data_ptr(), _handle(device, stream)))
+
+
 # ------------------------------------------------------------- wire (f4)
 MSG_HEADER, MSG_VOTE, MSG_CERTIFICATE, MSG_CERT_REQUEST = 0, 1, 2, 3
 WIRE_ETRUNC, WIRE_EFORMAT, WIRE_EKEY = -10, -11, -12
@@ -856,8 +887,9 @@ class AggregationQueue:
     """Python face of the native coalescing stage (coa_queue_*): submit
     header/vote signatures, certificate vote batches, whole certificates and
     worker batch digests from any thread, get a concurrent.futures.Future per
-    request -- True (Ok) / False (Err) for signatures and vote batches, the
-    CERT_BAD_* bits for certificates, the 32-byte Digest for digests; the
+    request -- True (Ok) / False (Err) for signatures, whole votes and vote
+    batches, the CERT_BAD_* bits for certificates and whole headers, the
+    32-byte Digest for digests; the
     engine error status raises EngineError in the future."""
 
     def __init__(self, max_batch=65536, max_delay_us=500):
@@ -923,6 +955,40 @@ class AggregationQueue:
                 self._borrowed.pop(key, None)
         self._submitted(key, rc)
         return fut
+
+    def submit_header(self, header_input, id_, author, signature):
+        """Future of Header::verify's crypto bits for one header: CERT_BAD_HEADER_ID
+        | CERT_BAD_HEADER_SIG (0 = both Ok), coa_header_verify_many's semantics."""
+        key, fut = self._register("certificate")
+        h = np.frombuffer(bytes(header_input), np.uint8).copy() if len(header_input) else np.zeros(1, np.uint8)
+        i = np.frombuffer(bytes(id_), np.uint8).copy()
+        a = np.frombuffer(bytes(author), np.uint8).copy()
+        sg = np.frombuffer(signature.flatten() if isinstance(signature, Signature) else bytes(signature),
+                           np.uint8).copy()
+        rc = lib().coa_queue_submit_header(self._q, _u8p(h), len(header_input), _u8p(i), _u8p(a), _u8p(sg), self._cb,
+                                           key)
+        self._submitted(key, rc)
+        return fut
+
+    def submit_vote(self, id_, round_, origin, author, signature):
+        """Future of Vote::verify's signature check, True (Ok) / False (Err);
+        Vote::digest is hashed by the engine (coa_vote_verify_many's semantics)."""
+        key, fut = self._register()
+        i = np.frombuffer(bytes(id_), np.uint8).copy()
+        o = np.frombuffer(bytes(origin), np.uint8).copy()
+        a = np.frombuffer(bytes(author), np.uint8).copy()
+        sg = np.frombuffer(signature.flatten() if isinstance(signature, Signature) else bytes(signature),
+                           np.uint8).copy()
+        rc = lib().coa_queue_submit_vote(self._q, _u8p(i), int(round_), _u8p(o), _u8p(a), _u8p(sg), self._cb, key)
+        self._submitted(key, rc)
+        return fut
+
+    def message_stats(self):
+        """coa_queue_message_stats: header and vote requests, and the windows
+        that took the latency / the throughput message kernels."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _check(lib().coa_queue_message_stats(self._q, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("headers", "votes", "latency_windows", "throughput_windows"), (x.value for x in v)))
 
     def submit_digest(self, data):
         """Future of Digest(Sha512(data)[..32]) (worker/src/processor.rs:38)."""

@@ -205,6 +205,66 @@ struct MsgArgs {
 size_t coa_msg_scratch_bytes(uint64_t n);
 hipError_t coa_launch_msg_verify(MsgArgs a, uint32_t* pscr, hipStream_t s);
 
+// Latency variant for the headers and votes of one window (k_msg_verify_lat,
+// the shape of k_cert_verify_lat): blocks [0, nh) check the headers' digests,
+// blocks [nh, 2 nh + nv) run one strict signature job each -- the nh headers'
+// (message ids[i]) and then the nv votes' (message Vote::digest, hashed on the
+// job's wave 0).  Status word i < nh belongs to header i, word nh + j to vote
+// j, with k_msg_verify's bits.  host_res / done_ctr / tag as in CertArgs.
+struct MsgLatArgs {
+  const uint8_t* hdr_data;    // Header::digest inputs, concatenated
+  const uint64_t* hdr_off;    // [nh + 1]
+  const uint32_t* ids;        // [nh][8]  header.id
+  const uint32_t* hauthors;   // [nh][8]
+  const uint32_t* hsigs;      // [nh][16] R || s
+  const uint32_t* vids;       // [nv][8]  vote.id
+  const uint64_t* vrounds;    // [nv]
+  const uint32_t* vorigins;   // [nv][8]
+  const uint32_t* vauthors;   // [nv][8]
+  const uint32_t* vsigs;      // [nv][16]
+  uint32_t nh, nv;
+  const uint32_t* keys;
+  const uint32_t* kflags;
+  const uint32_t* ktabs;
+  uint32_t nk;
+  const uint32_t* comb;
+  uint32_t* status;           // [nh + nv], zero at launch
+  uint32_t* host_res = nullptr;
+  uint32_t* done_ctr = nullptr;
+  uint32_t tag = 0;
+  uint32_t total_blocks = 0;  // set by the launcher
+};
+hipError_t coa_launch_msg_verify_lat(MsgLatArgs a, hipStream_t s);
+
+// Device-resident entries of k_msg_verify_lat (the aggregation queue's
+// message windows, coa_queue_hip.cpp; not part of the public header).  The
+// arrays are device pointers laid out as coa_header_verify_many_device /
+// coa_vote_verify_many_device take them; either count may be zero.
+struct CoaMsgLatIn {
+  const uint8_t* hdr_data;
+  const uint64_t* hdr_off;
+  const uint8_t *hids, *hauthors, *hsigs;
+  uint64_t nh;
+  const uint8_t* vids;
+  const uint64_t* vrounds;
+  const uint8_t *vorigins, *vauthors, *vsigs;
+  uint64_t nv;
+};
+// Status mode: d_status [nh + nv] is zeroed on the stream, then written.
+extern "C" int coa_msg_lat_verify_device(int device, const CoaMsgLatIn* in, uint32_t* d_status, void* stream);
+// Publish mode, at most 64 messages: the last block writes (tag << 8) | status
+// per message into host_res (page-locked, polled by the caller) and re-zeroes
+// d_ctr[0..64] (65 device words, zero before the first call).
+extern "C" int coa_msg_lat_verify_publish(int device, const CoaMsgLatIn* in, uint32_t* d_ctr, uint32_t* host_res,
+                                          uint32_t tag, void* stream);
+
+// The exact decision of the messages the message kernels left open (raw words
+// with COA_CST_UNCACHED; the others pass through): verify_strict over the id
+// (rounds null: headers) or over Vote::digest (votes) through the uncached
+// path.  Host arrays; raw[i] becomes (its header-id bit) | the signature bit.
+extern "C" int coa_message_resolve_raw(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins,
+                                       const uint8_t* authors, const uint8_t* sigs, size_t n, uint32_t* raw);
+
 // Row-parallel field arithmetic (coa_fe_wave.h) against coa_fe.h, one wave per
 // input x_i (32 LE bytes, any value < 2^256): out[i] bit0 pow_p58, bit1
 // invert, bit2 x_i * x_{i+1}, bit3 decompression of x_i as an encoding

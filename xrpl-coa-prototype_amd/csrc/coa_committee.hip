@@ -603,7 +603,54 @@ extern "C" int coa_lat_trace_hdr(unsigned long long* out) {
 // acq_rel fences this replaced cost an L2 write-back and an L1 invalidate
 // each (buffer_wbl2 / buffer_inv sc1), four and three of them on the
 // critical block's tail.
-COA_DEV void lat_block_done(const CertArgs& a, uint32_t c, uint32_t bits) {
+// What differs between the latency kernels (A: CertArgs, k_cert_verify_lat,
+// or MsgLatArgs, k_msg_verify_lat): lat_digests header-digest blocks lead the
+// grid, lat_words status words are published, and lat_job names signature job
+// `job`: its status word, its signature, its key, the 32-byte id it signs
+// (strict: dalek's verify_strict rule; digest: the message is SHA-512(id ||
+// round LE || origin)[..32] of *round and origin, hashed on wave 0).
+struct LatJob {
+  bool strict, digest;
+  uint32_t c;
+  const uint32_t *sig, *pk, *id, *origin;
+  const uint64_t* round;
+};
+COA_DEV uint32_t lat_digests(const CertArgs& a) { return a.nc; }
+COA_DEV uint32_t lat_words(const CertArgs& a) { return a.nc; }
+COA_DEV LatJob lat_job(const CertArgs& a, uint32_t job) {
+  const bool hdr = job < a.nc;
+  const uint32_t vi = job - a.nc;
+  const uint32_t c = hdr ? job : vote_cert_u(a.voff, a.nc, vi);
+  LatJob j;
+  j.strict = hdr;
+  j.digest = !hdr;
+  j.c = c;
+  j.sig = sel_ptr(hdr, a.hsigs + (uint64_t)c * 16, a.vsigs + (uint64_t)vi * 16);
+  j.pk = sel_ptr(hdr, a.origins + (uint64_t)c * 8, a.vpks + (uint64_t)vi * 8);
+  j.id = a.ids + (uint64_t)c * 8;
+  j.origin = a.origins + (uint64_t)c * 8;
+  j.round = a.rounds + c;
+  return j;
+}
+COA_DEV uint32_t lat_digests(const MsgLatArgs& a) { return a.nh; }
+COA_DEV uint32_t lat_words(const MsgLatArgs& a) { return a.nh + a.nv; }
+COA_DEV LatJob lat_job(const MsgLatArgs& a, uint32_t job) {
+  const bool hdr = job < a.nh;
+  const uint32_t vi = job - a.nh;
+  LatJob j;
+  j.strict = true;
+  j.digest = !hdr;
+  j.c = job;
+  j.sig = sel_ptr(hdr, a.hsigs + (uint64_t)job * 16, a.vsigs + (uint64_t)vi * 16);
+  j.pk = sel_ptr(hdr, a.hauthors + (uint64_t)job * 8, a.vauthors + (uint64_t)vi * 8);
+  j.id = sel_ptr(hdr, a.ids + (uint64_t)job * 8, a.vids + (uint64_t)vi * 8);
+  j.origin = a.vorigins + (uint64_t)vi * 8;  // read only when digest
+  j.round = a.vrounds + vi;
+  return j;
+}
+
+template <class A>
+COA_DEV void lat_block_done(const A& a, uint32_t c, uint32_t bits) {
   if (bits) (void)__hip_atomic_fetch_or(a.status + c, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!a.host_res) return;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -611,16 +658,17 @@ COA_DEV void lat_block_done(const CertArgs& a, uint32_t c, uint32_t bits) {
   if (old + 1 != a.total_blocks) return;
   HDR_MARK(6)
   __hip_atomic_store(a.done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (uint32_t k = 0; k < a.nc; k++) {
+  for (uint32_t k = 0; k < lat_words(a); k++) {
     const uint32_t st = __hip_atomic_exchange(a.status + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(a.host_res + k, (a.tag << 8) | (st & 0xffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
-COA_DEV void cert_lat_body(const CertArgs& a) {
+template <class A>
+COA_DEV void cert_lat_body(const A& a) {
   const uint32_t wave = coa_sha::uni(threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63;
-  if (blockIdx.x < a.nc) {  // header digest: schedule in parallel, rounds on wave 0
+  if (blockIdx.x < lat_digests(a)) {  // header digest: schedule in parallel, rounds on wave 0
     __shared__ uint64_t kw_lds[KW_CHUNK * 80];
     const uint32_t c = blockIdx.x;
     if (c == 0 && threadIdx.x == 0) { HDR_MARK(0) }
@@ -678,11 +726,11 @@ COA_DEV void cert_lat_body(const CertArgs& a) {
     cmp.ready = 0;
   }
   __syncthreads();
-  const uint32_t job = blockIdx.x - a.nc;
-  const bool hdr = job < a.nc;
-  const uint32_t vi = job - a.nc;
-  const uint32_t c = hdr ? job : vote_cert_u(a.voff, a.nc, vi);
-  const uint32_t* sig = sel_ptr(hdr, a.hsigs + (uint64_t)c * 16, a.vsigs + (uint64_t)vi * 16);
+  const uint32_t job = blockIdx.x - lat_digests(a);
+  const LatJob J = lat_job(a, job);
+  const bool hdr = J.strict;
+  const uint32_t c = J.c;
+  const uint32_t* sig = J.sig;
   uint32_t rw[8];
   load8u(rw, sig);
   LAT_MARK(wave, 0)
@@ -719,9 +767,9 @@ COA_DEV void cert_lat_body(const CertArgs& a) {
     load8u(dg, sig + 8);
   } else {
     uint32_t pk[8], sw[8], msg[8];
-    load8u(pk, sel_ptr(hdr, a.origins + (uint64_t)c * 8, a.vpks + (uint64_t)vi * 8));
+    load8u(pk, J.pk);
     load8u(sw, sig + 8);
-    load8u(msg, a.ids + (uint64_t)c * 8);
+    load8u(msg, J.id);
     slot = key_lookup_u(a.keys, a.nk, pk);
     if (slot < 0) {
       bits = COA_CST_UNCACHED;
@@ -729,14 +777,14 @@ COA_DEV void cert_lat_body(const CertArgs& a) {
     } else {
       uint64_t st[8];
       uint32_t h[16];
-      if (!hdr) {  // Certificate::digest on the scalar unit
+      if (J.digest) {  // Certificate::digest / Vote::digest on the scalar unit
         uint32_t in[18];
-        const uint64_t rd = uni64(a.rounds[c]);
+        const uint64_t rd = uni64(*J.round);
 #pragma unroll
         for (int i = 0; i < 8; i++) in[i] = msg[i];
         in[8] = (uint32_t)rd;
         in[9] = (uint32_t)(rd >> 32);
-        load8u(in + 10, a.origins + (uint64_t)c * 8);
+        load8u(in + 10, J.origin);
         coa_sha::hash_words<18>(st, in);
         coa_sha::state_to_le_words(h, st);
 #pragma unroll
@@ -799,6 +847,12 @@ COA_DEV void cert_lat_body(const CertArgs& a) {
 }
 
 __global__ void __launch_bounds__(192) k_cert_verify_lat(CertArgs a) { cert_lat_body(a); }
+
+// Header::verify / Vote::verify crypto of one window's messages, latency
+// shape (MsgLatArgs, coa_committee.h): the body above with every signature
+// job strict.  A header's signature job signs ids[i] as given, so it runs
+// beside that header's digest block, not after it.
+__global__ void __launch_bounds__(192) k_msg_verify_lat(MsgLatArgs a) { cert_lat_body(a); }
 
 // The same with the certificate's arrays read from the kernel arguments.  The
 // buffer is addressed through the kernarg segment pointer (ci is the only
@@ -1128,6 +1182,13 @@ hipError_t coa_launch_cert_verify(CertArgs a, int lanes_per_sig, uint32_t* pscr,
   else
     hipLaunchKernelGGL(k_cert_verify<2>, dim3((uint32_t)(a.hdr_blocks + lanes / 256)), dim3(256), 0, s, a, pscr,
                        cert_tp_jcap(jobs, lanes));
+  return hipGetLastError();
+}
+
+hipError_t coa_launch_msg_verify_lat(MsgLatArgs a, hipStream_t s) {
+  if (a.nh + a.nv == 0) return hipSuccess;
+  a.total_blocks = 2 * a.nh + a.nv;
+  hipLaunchKernelGGL(k_msg_verify_lat, dim3(a.total_blocks), dim3(192), 0, s, a);
   return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // Aggregation queue: the pre-verification stage between
 // PrimaryReceiverHandler::dispatch (primary/src/primary.rs:223-244) and
 // Core (primary/src/core.rs:349-389).  Core verifies one message at a time;
-// this stage collects pending header/vote signatures, vote batches, whole
+// this stage collects pending header/vote signatures, whole headers and
+// votes (Header::verify / Vote::verify with their digests), vote batches, whole
 // certificates and worker batch digests from any number of producer threads
 // and launches them as a few large GPU calls.  Modelled on the reference's
 // SignatureService (crypto/src/lib.rs:222-250): a request channel in, a
@@ -74,7 +75,7 @@ namespace {
 using coa_q::Launch;
 using coa_q::Window;
 
-enum Kind : uint8_t { K_VERIFY, K_BATCH, K_CERT, K_DIGEST };
+enum Kind : uint8_t { K_VERIFY, K_BATCH, K_CERT, K_DIGEST, K_HEADER, K_VOTE };
 
 inline void cpu_relax() {
 #if defined(__x86_64__)
@@ -141,7 +142,7 @@ struct Flight {
   int64_t t_launch = 0;  // ns, when the collector handed the window to the backend
 };
 
-// A part's requests the backend left open (Window::c_defer, g_defer), with
+// A part's requests the backend left open (Window::c_defer, m_defer, g_defer), with
 // the part's window (moved out of the flight, not recycled): the resolver
 // thread decides them and answers their callbacks.
 struct Deferred {
@@ -151,7 +152,9 @@ struct Deferred {
 };
 
 inline bool is_deferred(const Req& r, const Window& w) {
-  return (r.kind == K_CERT && w.is_deferred_cert(r.idx)) || (r.kind == K_BATCH && w.g_defer);
+  return (r.kind == K_CERT && w.is_deferred_cert(r.idx)) || (r.kind == K_BATCH && w.g_defer) ||
+         (r.kind == K_HEADER && w.is_deferred_msg(r.idx)) ||
+         (r.kind == K_VOTE && w.is_deferred_msg((uint32_t)w.nhd + r.idx));
 }
 
 std::atomic<uint64_t> g_queue_ids{1};
@@ -322,6 +325,7 @@ struct Lane {
   double m_window_max_at_ms = 0.0, m_window_max_dev_us = 0.0;
   uint32_t m_window_max_kinds = 0;
   uint64_t m_deferred = 0, m_passes = 0;
+  uint64_t m_hdr = 0, m_vote = 0, m_msg_lat = 0, m_msg_tp = 0;  // coa_queue_message_stats
   double m_resolve_us_max = 0.0;
   double m_stage_us[COA_QSTAGES] = {};
 
@@ -588,6 +592,7 @@ struct Lane {
       for (Part& p : f.parts) {
         if (rc != COA_OK) {
           p.w->c_defer.clear();
+          p.w->m_defer.clear();
           p.w->g_defer = false;
         }
         any_defer = any_defer || p.w->deferred();
@@ -628,6 +633,8 @@ struct Lane {
             case K_BATCH: r.cb(r.user, rc, w.g_out.data() + r.idx, 1); break;
             case K_CERT: r.cb(r.user, rc, w.c_out.data() + r.idx, 1); break;
             case K_DIGEST: r.cb(r.user, rc, w.d_out.data() + (size_t)r.idx * 32, 32); break;
+            case K_HEADER: r.cb(r.user, rc, w.hd_out.data() + r.idx, 1); break;
+            case K_VOTE: r.cb(r.user, rc, w.vt_out.data() + r.idx, 1); break;
           }
         }
       };
@@ -679,7 +686,11 @@ struct Lane {
       m_wait_max = std::max(m_wait_max, wmax);
       m_requests += nreq - ndef;
       for (int k = 0; k < COA_QSTAGES; k++) m_stage_us[k] += (double)f.L.stage_ns[k] * 1e-3;
-      m_sig += f.L.nv;
+      m_sig += f.L.nv + f.L.nhd + f.L.nvt;  // a message is one signature
+      m_hdr += f.L.nhd;
+      m_vote += f.L.nvt;
+      if (f.L.msg_route == Launch::MSG_LATENCY) m_msg_lat++;
+      if (f.L.msg_route == Launch::MSG_THROUGHPUT) m_msg_tp++;
       m_batch += f.L.ng;
       m_cert += f.L.nc;
       m_dig += f.L.nd;
@@ -730,6 +741,7 @@ struct Lane {
       if (rc != COA_OK) {
         for (Window* w : ws) {  // "failed" outputs with the engine error
           for (uint32_t c : w->c_defer) w->c_out[c] = 7;
+          for (uint32_t m : w->m_defer) (m < w->nhd ? w->hd_out[m] : w->vt_out[m - w->nhd]) = m < w->nhd ? 3 : 1;
           if (w->g_defer) w->g_out.assign(w->ng, 1);
         }
       }
@@ -746,6 +758,10 @@ struct Lane {
           hist[wait_bucket(us)]++;
           if (r.kind == K_CERT)
             r.cb(r.user, rc, w.c_out.data() + r.idx, 1);
+          else if (r.kind == K_HEADER)
+            r.cb(r.user, rc, w.hd_out.data() + r.idx, 1);
+          else if (r.kind == K_VOTE)
+            r.cb(r.user, rc, w.vt_out.data() + r.idx, 1);
           else
             r.cb(r.user, rc, w.g_out.data() + r.idx, 1);
           n++;
@@ -787,6 +803,7 @@ struct Lane {
     m_epoch_ns = now_ns();
     m_window_max_at_ms = m_window_max_dev_us = 0.0;
     m_deferred = m_passes = 0;
+    m_hdr = m_vote = m_msg_lat = m_msg_tp = 0;
     m_resolve_us_max = 0.0;
     std::fill(m_stage_us, m_stage_us + COA_QSTAGES, 0.0);
     be->reset_grows();
@@ -1034,6 +1051,44 @@ int coa_queue_submit_digest(coa_queue* q, const uint8_t* data, size_t len, coa_v
   if (len) w.d_data.insert(w.d_data.end(), data, data + len);
   w.d_offs.push_back(w.d_data.size());
   submitted(ln, sh, sl, K_DIGEST, (uint32_t)w.nd++, 1, cb, user, 1, t_in);
+  return COA_OK;
+}
+
+int coa_queue_submit_header(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
+                            const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
+  if (!q || (header_len && !header_data) || !id || !author || !sig || !cb) return COA_EINVAL;
+  COA_Q_INTAKE(q, K_HEADER)
+  if (header_len) w.hd_data.insert(w.hd_data.end(), header_data, header_data + header_len);
+  w.hd_offs.push_back(w.hd_data.size());
+  put<32>(w.hd_ids, id);
+  put<32>(w.hd_authors, author);
+  put<64>(w.hd_sigs, sig);
+  submitted(ln, sh, sl, K_HEADER, (uint32_t)w.nhd++, 1, cb, user, 1, t_in);
+  return COA_OK;
+}
+
+int coa_queue_submit_vote(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
+                          const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
+  if (!q || !id || !origin || !author || !sig || !cb) return COA_EINVAL;
+  COA_Q_INTAKE(q, K_VOTE)
+  put<32>(w.vt_ids, id);
+  w.vt_rounds.push_back(round);
+  put<32>(w.vt_origins, origin);
+  put<32>(w.vt_authors, author);
+  put<64>(w.vt_sigs, sig);
+  submitted(ln, sh, sl, K_VOTE, (uint32_t)w.nvt++, 1, cb, user, 1, t_in);
+  return COA_OK;
+}
+
+int coa_queue_message_stats(coa_queue* q, uint64_t* headers, uint64_t* votes, uint64_t* latency_windows,
+                            uint64_t* throughput_windows) {
+  if (!q) return COA_EINVAL;
+  Lane& L = q->lanes[coa_q::LANE_VERIFY];
+  std::lock_guard<std::mutex> l(L.mu);
+  if (headers) *headers = L.m_hdr;
+  if (votes) *votes = L.m_vote;
+  if (latency_windows) *latency_windows = L.m_msg_lat;
+  if (throughput_windows) *throughput_windows = L.m_msg_tp;
   return COA_OK;
 }
 

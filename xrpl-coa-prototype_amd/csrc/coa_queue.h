@@ -52,6 +52,21 @@ struct Window {
   std::vector<uint8_t> d_data;
   std::vector<uint64_t> d_offs;  // nd + 1
   std::vector<uint8_t> d_out;    // nd x 32
+  // whole headers (coa_header_verify_many semantics): the Header::digest
+  // bytes owned, concatenated, header i at [hd_offs[i], hd_offs[i + 1])
+  size_t nhd = 0;
+  std::vector<uint8_t> hd_data, hd_ids, hd_authors, hd_sigs;  // bytes, nhd x 32, 32, 64
+  std::vector<uint64_t> hd_offs;                              // nhd + 1
+  std::vector<uint8_t> hd_out;                                // nhd status bytes (COA_CERT_BAD_HEADER_* bits)
+  // whole votes (coa_vote_verify_many semantics)
+  size_t nvt = 0;
+  std::vector<uint8_t> vt_ids, vt_origins, vt_authors, vt_sigs;  // nvt x 32, 32, 32, 64
+  std::vector<uint64_t> vt_rounds;                               // nvt
+  std::vector<uint8_t> vt_out;                                   // nvt verdicts
+  // Messages whose author is outside the registered committee, left open for
+  // the resolver (ascending): header i as i, vote j as nhd + j.  An open
+  // header's hd_out already holds its digest bit.
+  std::vector<uint32_t> m_defer;
   // Left open by Backend::complete (or retry) for the lane's resolver
   // (Backend::resolve): certificates the fused kernel could not decide alone
   // (their raw status words kept) and, with g_defer, every bare vote batch.
@@ -61,9 +76,10 @@ struct Window {
   bool g_defer = false;
   int64_t intake_ns = 0;          // producers' time copying requests in (COA_QSTAGE_INTAKE)
 
-  bool deferred() const { return !c_defer.empty() || (g_defer && ng); }
+  bool deferred() const { return !c_defer.empty() || !m_defer.empty() || (g_defer && ng); }
+  bool is_deferred_msg(uint32_t m) const { return std::binary_search(m_defer.begin(), m_defer.end(), m); }
   bool is_deferred_cert(uint32_t c) const { return std::binary_search(c_defer.begin(), c_defer.end(), c); }
-  size_t items() const { return nv + nd + nc + c_votes + g_offs.back(); }
+  size_t items() const { return nv + nd + nc + c_votes + g_offs.back() + nhd + nvt; }
   // Owned refs' offsets -> pointers into c_own (which no longer changes once
   // the collector has taken the window).
   void bind() {
@@ -82,8 +98,11 @@ struct Window {
     g_out.assign(ng, 1);
     c_out.assign(nc, 7);
     d_out.assign(nd * 32, 0);
+    hd_out.assign(nhd, 3);
+    vt_out.assign(nvt, 1);
     c_raw.clear();
     c_defer.clear();
+    m_defer.clear();
     g_defer = false;
   }
   // Capacity for the largest window the lane's collector closes (`items` =
@@ -107,16 +126,27 @@ struct Window {
     // 3: those regrow)
     c_own.reserve(items * 96 + (items / 16 + 1) * 4224);
     c_refs.reserve(items / 16 + 1);
+    // votes 168 B each; headers' fixed fields, their bytes grow on demand
+    for (auto* v : {&vt_ids, &vt_origins, &vt_authors, &hd_ids, &hd_authors}) v->reserve(items * 32);
+    vt_sigs.reserve(items * 64), hd_sigs.reserve(items * 64);
+    vt_rounds.reserve(items), hd_offs.reserve(items + 1);
   }
   // Empty again for the next intake, keeping every vector's capacity (the
   // queue recycles answered windows, so a window fills without reallocating
   // under the intake lock).
   void reset() {
-    nv = ng = nc = nd = 0;
+    nv = ng = nc = nd = nhd = nvt = 0;
     intake_ns = 0;
     g_defer = false;
     c_raw.clear();
     c_defer.clear();
+    m_defer.clear();
+    for (auto* v : {&hd_data, &hd_ids, &hd_authors, &hd_sigs, &hd_out, &vt_ids, &vt_origins, &vt_authors, &vt_sigs,
+                    &vt_out})
+      v->clear();
+    vt_rounds.clear();
+    hd_offs.clear();
+    hd_offs.push_back(0);
     for (auto* v : {&v_msgs, &v_pks, &v_sigs, &v_out, &g_msgs, &g_pks, &g_sigs, &g_out, &c_own, &c_out, &d_data, &d_out})
       v->clear();
     for (auto* v : {&g_offs, &d_offs}) v->clear();
@@ -135,6 +165,11 @@ struct Launch {
   size_t hbytes = 0;   // certificate header bytes
   size_t dbytes = 0;   // digest input bytes
   size_t gvotes = 0;   // bare-batch votes
+  size_t nhd = 0, nvt = 0;  // whole headers, whole votes
+  size_t hdbytes = 0;       // the headers' Header::digest bytes
+  // the route the backend gave the launch's messages (coa_queue_message_stats)
+  enum { MSG_NONE = 0, MSG_LATENCY, MSG_THROUGHPUT };
+  int msg_route = MSG_NONE;
   int rc = COA_OK;     // engine status (negative = failure), set by the backend
   int slot = -1;       // backend slot the launch ran on
   int attempts = 0;    // launches of this window (1 + retries)
@@ -150,10 +185,11 @@ struct Launch {
   // COA_QUEUE_KIND_* bits of the kinds the launch holds
   uint32_t kinds() const {
     return (nv ? COA_QUEUE_KIND_SIGNATURES : 0u) | (ng ? COA_QUEUE_KIND_BATCHES : 0u) |
-           (nc ? COA_QUEUE_KIND_CERTIFICATES : 0u) | (nd ? COA_QUEUE_KIND_DIGESTS : 0u);
+           (nc ? COA_QUEUE_KIND_CERTIFICATES : 0u) | (nd ? COA_QUEUE_KIND_DIGESTS : 0u) |
+           (nhd ? COA_QUEUE_KIND_HEADERS : 0u) | (nvt ? COA_QUEUE_KIND_VOTES : 0u);
   }
   void tally() {
-    nv = ng = nc = nd = nvotes = hbytes = dbytes = gvotes = 0;
+    nv = ng = nc = nd = nvotes = hbytes = dbytes = gvotes = nhd = nvt = hdbytes = 0;
     for (const Window* w : parts) {
       nv += w->nv;
       ng += w->ng;
@@ -163,12 +199,16 @@ struct Launch {
       hbytes += w->c_hbytes;
       dbytes += w->d_data.size();
       gvotes += w->g_offs.back();
+      nhd += w->nhd;
+      nvt += w->nvt;
+      hdbytes += w->hd_data.size();
     }
   }
-  size_t items() const { return nv + nd + nc + nvotes + gvotes; }
+  size_t items() const { return nv + nd + nc + nvotes + gvotes + nhd + nvt; }
   void reset_outputs() {
     for (Window* w : parts) w->reset_outputs();
     rc = COA_OK;
+    msg_route = MSG_NONE;
   }
 };
 
@@ -200,7 +240,8 @@ class Backend {
   // Number of device contexts retries can go to (at least 1).
   virtual int devices() const = 0;
   // Decides what complete() / retry() left open in the windows `ws`
-  // (Window::c_defer, g_defer), writing their c_out / g_out.  Called by the
+  // (Window::c_defer, m_defer, g_defer), writing their c_out / hd_out / vt_out
+  // / g_out.  Called by the
   // lane's resolver thread -- concurrently with launch() and complete() of
   // later windows, never with itself.  Returns the engine status.
   virtual int resolve(const std::vector<Window*>& ws) {

@@ -40,6 +40,16 @@
 //                 second fused launch -- while the rest of the window is
 //                 answered at once.  A window with certificates pins its
 //                 device's key-cache generation from launch to completion
+//   headers, votes  the committee-comb message kernels, Header::digest checked
+//                 and Vote::digest hashed on the device: alone in a window of
+//                 at most 64 messages, the latency kernel in publish mode
+//                 (Slot::mpub); a window of at most COA_QUEUE_MSG_LAT_MAX
+//                 messages, the latency kernel with its status words staged
+//                 (coa_msg_lat_verify_device); a larger one,
+//                 coa_header_verify_many_device / coa_vote_verify_many_device.
+//                 Messages by authors outside the registered committee
+//                 (COA_CST_UNCACHED) are left open (Window::m_defer) and
+//                 decided by resolve() with coa_message_resolve_raw
 //   digests       coa_sha512_many_device (worker/src/processor.rs:38)
 //   vote batches  coa_ed25519_verify_batch_groups in resolve() (host
 //                 pointers; bare batches are rare next to whole certificates)
@@ -73,7 +83,13 @@
 // nothing and shorten the wait for a slot: at C4's 1,000 batches/s, 8 slots
 // give p50 16.0 ms against 19.6 with 4 (profiles/r05_digest_slots_ab.jsonl)
 #define COA_QUEUE_DIGEST_SLOTS_DEFAULT 8
-#define COA_LAT_RES_WORDS 64  // result words of an inline latency or published certificate window
+#define COA_LAT_RES_WORDS 64  // result words of an inline latency or published certificate / message window
+// Largest message window (headers + votes) the latency kernel takes
+// (COA_QUEUE_MSG_LAT_MAX, read at queue creation): the largest window size of
+// tools/queue_message_ab.py's device-side sweep at which k_msg_verify_lat was
+// not slower than k_msg_verify, for headers and for votes
+// (profiles/queue_message_ab.json)
+#define COA_QUEUE_MSG_LAT_MAX_DEFAULT 512
 
 namespace {
 
@@ -116,8 +132,12 @@ struct Slot {
   // fits, coa_certificate_verify_publish); dctr is its device counter block
   bool cpub = false;
   uint32_t* dctr = nullptr;  // 65 device words, zero between launches
+  // a window of at most COA_LAT_RES_WORDS headers and votes and nothing else
+  // the device runs: one H2D copy, the message latency kernel, its last block
+  // publishing the status words into lres (coa_msg_lat_verify_publish)
+  bool mpub = false;
   // output offsets of the current launch
-  size_t o_v = 0, o_c = 0, o_d = 0;
+  size_t o_v = 0, o_c = 0, o_d = 0, o_m = 0;
 };
 
 // A slot's staging grows geometrically (twice what a window needs) and an
@@ -280,7 +300,9 @@ void free_slot(Slot& sl) {
 
 class HipBackend : public coa_q::Backend {
  public:
-  explicit HipBackend(int lane) : lane_(lane) {}
+  explicit HipBackend(int lane) : lane_(lane) {
+    if (const char* e = getenv("COA_QUEUE_MSG_LAT_MAX")) msg_lat_max_ = (size_t)strtoull(e, nullptr, 10);
+  }
   ~HipBackend() override {
     for (Slot& sl : slots_) free_slot(sl);
     for (Slot& sl : rescue_) free_slot(sl);
@@ -526,12 +548,20 @@ class HipBackend : public coa_q::Backend {
                  i_cor = take(L.nc * 32), i_chs = take(L.nc * 64), i_crd = take(L.nc * 8),
                  i_cvp = take(L.nvotes * 32), i_cvs = take(L.nvotes * 64), i_cvo = take((L.nc + 1) * 8);
     const size_t i_dd = take(L.dbytes + 16), i_do = take((L.nd + 1) * 8);
+    const size_t msgs = L.nhd + L.nvt;
+    const size_t i_hd = take(L.nhd ? L.hdbytes + 16 : 0), i_hdo = take(L.nhd ? (L.nhd + 1) * 8 : 0),
+                 i_hid = take(L.nhd * 32), i_hau = take(L.nhd * 32), i_hsg = take(L.nhd * 64);
+    const size_t i_tid = take(L.nvt * 32), i_trd = take(L.nvt * 8), i_tor = take(L.nvt * 32),
+                 i_tau = take(L.nvt * 32), i_tsg = take(L.nvt * 64);
     const size_t in_bytes = o;
     o = 0;
     sl.o_v = take(sl.lat ? L.nv * 4 : L.nv);
     sl.o_c = take(L.nc * 4);
     sl.o_d = take(L.nd * 64);
+    sl.o_m = take(msgs * 4);  // the headers' status words, then the votes'
     const size_t out_bytes = o;
+    const bool msg_lat = msgs > 0 && msgs <= msg_lat_max_;
+    const size_t ws_m = (msgs && !msg_lat) ? coa_message_workspace_bytes(std::max(L.nhd, L.nvt)) : 0;
     const size_t ws_v = L.nv ? coa_verify_workspace_bytes(L.nv) : 0;
     const size_t ws_c = L.nc ? coa_cert_scratch_bytes(L.nc + L.nvotes, keysort_) : 0;
     const size_t caps0 = sl.cap_hin + sl.cap_hout + sl.cap_din + sl.cap_dout + sl.cap_ws;
@@ -539,7 +569,7 @@ class HipBackend : public coa_q::Backend {
         grow_pinned(sl.hout, sl.cap_hout, out_bytes, sl.grave) != hipSuccess ||
         grow_dev(sl.din, sl.cap_din, in_bytes, sl.grave) != hipSuccess ||
         grow_dev(sl.dout, sl.cap_dout, out_bytes, sl.grave) != hipSuccess ||
-        grow_dev(sl.ws, sl.cap_ws, std::max(ws_v, ws_c) + 256, sl.grave) != hipSuccess)
+        grow_dev(sl.ws, sl.cap_ws, std::max(std::max(ws_v, ws_c), ws_m) + 256, sl.grave) != hipSuccess)
       return COA_ENOMEM;
     if (sl.cap_hin + sl.cap_hout + sl.cap_din + sl.cap_dout + sl.cap_ws != caps0) grows_++;
     uint8_t* h = static_cast<uint8_t*>(sl.hin);
@@ -549,7 +579,9 @@ class HipBackend : public coa_q::Backend {
     auto copy = [&bulk](void* dst, const void* src, size_t bytes) {
       if (bytes) bulk.push_back({dst, src, bytes});
     };
-    size_t v = 0, c = 0, cv = 0, hb = 0, dn = 0, db = 0;
+    size_t v = 0, c = 0, cv = 0, hb = 0, dn = 0, db = 0, mh = 0, mhb = 0, mt = 0;
+    uint64_t* hdo = reinterpret_cast<uint64_t*>(h + i_hdo);
+    if (L.nhd) hdo[0] = 0;
     uint64_t* cho = reinterpret_cast<uint64_t*>(h + i_cho);
     uint64_t* cvo = reinterpret_cast<uint64_t*>(h + i_cvo);
     uint64_t* dof = reinterpret_cast<uint64_t*>(h + i_do);
@@ -592,6 +624,23 @@ class HipBackend : public coa_q::Backend {
         dn += w->nd;
         db += w->d_data.size();
       }
+      if (w->nhd) {
+        copy(h + i_hd + mhb, w->hd_data.data(), w->hd_data.size());
+        for (size_t i = 1; i <= w->nhd; i++) hdo[mh + i] = mhb + w->hd_offs[i];
+        copy(h + i_hid + mh * 32, w->hd_ids.data(), w->nhd * 32);
+        copy(h + i_hau + mh * 32, w->hd_authors.data(), w->nhd * 32);
+        copy(h + i_hsg + mh * 64, w->hd_sigs.data(), w->nhd * 64);
+        mh += w->nhd;
+        mhb += w->hd_data.size();
+      }
+      if (w->nvt) {
+        copy(h + i_tid + mt * 32, w->vt_ids.data(), w->nvt * 32);
+        copy(h + i_trd + mt * 8, w->vt_rounds.data(), w->nvt * 8);
+        copy(h + i_tor + mt * 32, w->vt_origins.data(), w->nvt * 32);
+        copy(h + i_tau + mt * 32, w->vt_authors.data(), w->nvt * 32);
+        copy(h + i_tsg + mt * 64, w->vt_sigs.data(), w->nvt * 64);
+        mt += w->nvt;
+      }
     }
     size_t bulk_bytes = 0;
     for (const CoaCopySeg& g : bulk) bulk_bytes += g.bytes;
@@ -602,7 +651,7 @@ class HipBackend : public coa_q::Backend {
     }
     const auto t_enq = std::chrono::steady_clock::now();
     L.stage_ns[COA_QSTAGE_PACK] += ns_between(t_pack, t_enq);
-    if (L.nv + L.nc + L.nd == 0) return COA_OK;  // bare vote batches only: left to resolve()
+    if (L.nv + L.nc + L.nd + msgs == 0) return COA_OK;  // bare vote batches only: left to resolve()
     struct EnqClock {  // ENQUEUE stage: every return below
       coa_q::Launch& L;
       std::chrono::steady_clock::time_point t;
@@ -616,8 +665,9 @@ class HipBackend : public coa_q::Backend {
       L.enq_ns[k] += ns_between(t_mark, t);
       t_mark = t;
     };
-    sl.cpub = false;
-    sl.inl = inline_ok_ && sl.lat && L.nv <= COA_LAT_INLINE && L.nc == 0 && L.nd == 0 && lat_words(sl) != nullptr;
+    sl.cpub = sl.mpub = false;
+    sl.inl = inline_ok_ && sl.lat && L.nv <= COA_LAT_INLINE && L.nc == 0 && L.nd == 0 && msgs == 0 &&
+             lat_words(sl) != nullptr;
     if (sl.inl) {
       // a few signatures alone (Header::verify / Vote::verify at low load):
       // the packed records go in the kernel arguments and the verdict words
@@ -640,7 +690,7 @@ class HipBackend : public coa_q::Backend {
       mark(coa_q::Launch::ENQ_EVENT);
       return er == hipSuccess ? COA_OK : COA_EHIP;
     }
-    sl.cpub = inline_ok_ && L.nc > 0 && L.nc <= COA_LAT_RES_WORDS && L.nv == 0 && L.nd == 0 &&
+    sl.cpub = inline_ok_ && L.nc > 0 && L.nc <= COA_LAT_RES_WORDS && L.nv == 0 && L.nd == 0 && msgs == 0 &&
               lat_words(sl) != nullptr && ctr_words(sl) != nullptr;
     if (sl.cpub) {
       // certificates alone, few (Certificate::verify at low load): see Slot::cpub
@@ -673,6 +723,48 @@ class HipBackend : public coa_q::Backend {
     }
     uint8_t* d = static_cast<uint8_t*>(sl.din);
     uint8_t* dout = static_cast<uint8_t*>(sl.dout);
+    // the window's messages as the device entries take them
+    CoaMsgLatIn msg_in{};
+    if (L.nhd) {
+      msg_in.hdr_data = d + i_hd;
+      msg_in.hdr_off = reinterpret_cast<const uint64_t*>(d + i_hdo);
+      msg_in.hids = d + i_hid;
+      msg_in.hauthors = d + i_hau;
+      msg_in.hsigs = d + i_hsg;
+      msg_in.nh = L.nhd;
+    }
+    if (L.nvt) {
+      msg_in.vids = d + i_tid;
+      msg_in.vrounds = reinterpret_cast<const uint64_t*>(d + i_trd);
+      msg_in.vorigins = d + i_tor;
+      msg_in.vauthors = d + i_tau;
+      msg_in.vsigs = d + i_tsg;
+      msg_in.nv = L.nvt;
+    }
+    if (msgs) L.msg_route = msg_lat ? coa_q::Launch::MSG_LATENCY : coa_q::Launch::MSG_THROUGHPUT;
+    sl.mpub = inline_ok_ && msg_lat && msgs <= COA_LAT_RES_WORDS && L.nv == 0 && L.nc == 0 && L.nd == 0 &&
+              lat_words(sl) != nullptr && ctr_words(sl) != nullptr;
+    if (sl.mpub) {
+      // headers and votes alone, few (Header::verify / Vote::verify at low
+      // load): see Slot::mpub.  No status memset, no D2H copy, no event wait
+      std::memset(sl.lres, 0, msgs * sizeof(uint32_t));  // no tag matches 0
+      sl.ltag = (sl.ltag + 1) & 0xffffffu;
+      if (sl.ltag == 0) sl.ltag = 1;
+      if (hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, sl.s) != hipSuccess) return COA_EHIP;
+      mark(coa_q::Launch::ENQ_H2D);
+      sl.launched = true;
+      if (inject) return COA_EHIP;  // fault injection: the copy is in flight, the kernel never runs
+      if (!sl.keys) sl.keys = coa_keycache_pin(sl.dev);
+      coa_keycache_use(sl.keys);
+      mark(coa_q::Launch::ENQ_PIN);
+      const int rc = coa_msg_lat_verify_publish(sl.dev, &msg_in, sl.dctr, sl.lres, sl.ltag, sl.s);
+      coa_keycache_use(nullptr);
+      mark(coa_q::Launch::ENQ_LAUNCH);
+      if (rc != COA_OK) return rc;
+      const hipError_t er = hipEventRecord(sl.ev, sl.s);
+      mark(coa_q::Launch::ENQ_EVENT);
+      return er == hipSuccess ? COA_OK : COA_EHIP;
+    }
     if (hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, sl.s) != hipSuccess) return COA_EHIP;
     mark(coa_q::Launch::ENQ_H2D);
     sl.launched = true;
@@ -681,7 +773,7 @@ class HipBackend : public coa_q::Backend {
     // both read the committee key cache: the launch pins the current
     // generation until complete() (a registration meanwhile builds the next
     // one beside it) and its launches read that one
-    if ((sl.lat || L.nc) && !sl.keys) sl.keys = coa_keycache_pin(sl.dev);
+    if ((sl.lat || L.nc || msgs) && !sl.keys) sl.keys = coa_keycache_pin(sl.dev);
     coa_keycache_use(sl.keys);
     mark(coa_q::Launch::ENQ_PIN);
     if (L.nv && sl.lat)
@@ -697,6 +789,17 @@ class HipBackend : public coa_q::Backend {
           reinterpret_cast<const uint64_t*>(d + i_crd), d + i_cvp, d + i_cvs,
           reinterpret_cast<const uint64_t*>(d + i_cvo), L.nc, L.nvotes, reinterpret_cast<uint32_t*>(dout + sl.o_c),
           sl.ws, sl.s, keysort_ ? 1 : 0);
+    }
+    uint32_t* d_mst = reinterpret_cast<uint32_t*>(dout + sl.o_m);
+    if (rc == COA_OK && msg_lat) {
+      rc = coa_msg_lat_verify_device(sl.dev, &msg_in, d_mst, sl.s);
+    } else if (rc == COA_OK && msgs) {
+      if (L.nhd)
+        rc = coa_header_verify_many_device(sl.dev, msg_in.hdr_data, msg_in.hdr_off, msg_in.hids, msg_in.hauthors,
+                                           msg_in.hsigs, L.nhd, d_mst, sl.ws, sl.s);
+      if (rc == COA_OK && L.nvt)
+        rc = coa_vote_verify_many_device(sl.dev, msg_in.vids, msg_in.vrounds, msg_in.vorigins, msg_in.vauthors,
+                                         msg_in.vsigs, L.nvt, d_mst + L.nhd, sl.ws, sl.s);
     }
     if (rc == COA_OK && L.nd)
       rc = coa_sha512_many_device(sl.dev, d + i_dd, reinterpret_cast<const uint64_t*>(d + i_do), L.nd, dout + sl.o_d,
@@ -718,8 +821,8 @@ class HipBackend : public coa_q::Backend {
     const auto t_wait = std::chrono::steady_clock::now();
     if (sl.launched) {
       (void)hipSetDevice(sl.dev);
-      if (L.rc == COA_OK && (sl.inl || sl.cpub)) {
-        L.rc = poll_words(sl, sl.inl ? L.nv : L.nc);
+      if (L.rc == COA_OK && (sl.inl || sl.cpub || sl.mpub)) {
+        L.rc = poll_words(sl, sl.inl ? L.nv : sl.cpub ? L.nc : L.nhd + L.nvt);
       } else if (L.rc == COA_OK) {
         if (hipEventSynchronize(sl.ev) != hipSuccess) L.rc = COA_EHIP;
       } else {
@@ -731,8 +834,12 @@ class HipBackend : public coa_q::Backend {
     L.stage_ns[COA_QSTAGE_DEVICE_WAIT] += ns_between(t_wait, t_scatter);
     if (L.rc == COA_OK) {
       const uint8_t* h = static_cast<const uint8_t*>(sl.hout);
-      size_t v = 0, c = 0, dn = 0;
+      size_t v = 0, c = 0, dn = 0, mh = 0, mt = 0;
+      const uint32_t* mst = sl.mpub ? sl.lres : reinterpret_cast<const uint32_t*>(h + sl.o_m);
       for (coa_q::Window* w : L.parts) {
+        scatter_messages(*w, mst + mh, mst + L.nhd + mt);
+        mh += w->nhd;
+        mt += w->nvt;
         if (w->nv && sl.lat) {
           const uint32_t* words = (sl.inl ? sl.lres : reinterpret_cast<const uint32_t*>(h + sl.o_v)) + v;
           for (size_t i = 0; i < w->nv; i++) w->v_out[i] = (uint8_t)(words[i] & 0xffu);
@@ -779,6 +886,23 @@ class HipBackend : public coa_q::Backend {
       }
     }
     return COA_OK;
+  }
+
+  // Raw message status words (a published word's tag ignored) -> the
+  // headers' COA_CERT_BAD_HEADER_* bits and the votes' verdicts; a message by an
+  // author outside the committee is left open for resolve(), a header's
+  // digest bit kept.
+  static void scatter_messages(coa_q::Window& w, const uint32_t* hst, const uint32_t* vst) {
+    w.m_defer.clear();
+    for (size_t i = 0; i < w.nhd; i++) {
+      const bool open = (hst[i] & COA_CST_UNCACHED) != 0;
+      if (open) w.m_defer.push_back((uint32_t)i);
+      w.hd_out[i] = (uint8_t)(hst[i] & (open ? 1u : 3u));
+    }
+    for (size_t i = 0; i < w.nvt; i++) {
+      if (vst[i] & COA_CST_UNCACHED) w.m_defer.push_back((uint32_t)(w.nhd + i));
+      w.vt_out[i] = (vst[i] & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
+    }
   }
 
   // Raw certificate status words -> COA_CERT_* bits; the certificates the
@@ -828,6 +952,43 @@ class HipBackend : public coa_q::Backend {
         for (size_t g = 1; g <= w->ng; g++) go.push_back(go.back() + (w->g_offs[g] - w->g_offs[g - 1]));
       }
     }
+    // the open messages: verify_strict through the uncached path, the votes
+    // over Vote::digest (coa_message_resolve_raw)
+    std::vector<uint8_t> mi[2], mo, ma[2], ms[2];  // [0] headers, [1] votes
+    std::vector<uint64_t> mr;
+    std::vector<uint32_t> mraw[2];
+    for (const coa_q::Window* w : ws)
+      for (uint32_t m : w->m_defer) {
+        const bool vote = m >= w->nhd;
+        const size_t i = vote ? m - w->nhd : m;
+        const uint8_t* id = (vote ? w->vt_ids : w->hd_ids).data() + i * 32;
+        const uint8_t* au = (vote ? w->vt_authors : w->hd_authors).data() + i * 32;
+        const uint8_t* sg = (vote ? w->vt_sigs : w->hd_sigs).data() + i * 64;
+        mi[vote].insert(mi[vote].end(), id, id + 32);
+        ma[vote].insert(ma[vote].end(), au, au + 32);
+        ms[vote].insert(ms[vote].end(), sg, sg + 64);
+        if (vote) {
+          mo.insert(mo.end(), w->vt_origins.data() + i * 32, w->vt_origins.data() + i * 32 + 32);
+          mr.push_back(w->vt_rounds[i]);
+        }
+        mraw[vote].push_back(COA_CST_UNCACHED | (vote ? 0u : (uint32_t)(w->hd_out[i] & 1u)));
+      }
+    for (int vote = 0; vote < 2; vote++) {
+      if (mraw[vote].empty()) continue;
+      const int rc = coa_message_resolve_raw(mi[vote].data(), vote ? mr.data() : nullptr, vote ? mo.data() : nullptr,
+                                             ma[vote].data(), ms[vote].data(), mraw[vote].size(), mraw[vote].data());
+      if (rc != COA_OK) return rc;
+    }
+    size_t mj[2] = {0, 0};
+    for (coa_q::Window* w : ws)
+      for (uint32_t m : w->m_defer) {
+        const bool vote = m >= w->nhd;
+        const uint32_t st = mraw[vote][mj[vote]++];
+        if (vote)
+          w->vt_out[m - w->nhd] = (st & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
+        else
+          w->hd_out[m] = (uint8_t)(st & 3u);
+      }
     if (!raw.empty()) {
       std::vector<uint8_t> out(raw.size(), 7);
       const int rc = coa_certificate_resolve_raw(ids.data(), org.data(), hs.data(), rd.data(), vp.data(), vs.data(),
@@ -865,6 +1026,7 @@ class HipBackend : public coa_q::Backend {
   unsigned long long fault_every_ = 0, launches_ = 0;
   bool inline_ok_ = true;  // COA_QUEUE_INLINE
   bool keysort_ = true;     // COA_QUEUE_KEYSORT
+  size_t msg_lat_max_ = COA_QUEUE_MSG_LAT_MAX_DEFAULT;
 };
 
 }  // namespace

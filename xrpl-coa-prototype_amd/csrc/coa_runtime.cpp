@@ -1815,10 +1815,18 @@ int msg_shard(Dev& d, const MsgIn& in, size_t lo, size_t hi, uint32_t* raw) {
 // author is not registered through the uncached path: verify_strict over the
 // id (headers) or Vote::digest (votes).  A header's digest bit does not use
 // the cache and stands.
+int messages_resolve(const MsgIn& in, size_t n, uint32_t* st);
 int messages_impl(const MsgIn& in, size_t n, std::vector<uint32_t>& st) {
   st.assign(n, 0);
   int rc = for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int { return msg_shard(d, in, lo, hi, st.data()); });
   if (rc != COA_OK) return rc;
+  return messages_resolve(in, n, st.data());
+}
+
+// The re-decision alone (coa_message_resolve_raw: the aggregation queue's
+// resolver has the raw words already).
+int messages_resolve(const MsgIn& in, size_t n, uint32_t* st) {
+  int rc = COA_OK;
   std::vector<size_t> open;
   for (size_t i = 0; i < n; i++)
     if (st[i] & COA_CST_UNCACHED) open.push_back(i);
@@ -2774,6 +2782,75 @@ int coa_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8
   if (rc != COA_OK) return rc;
   for (size_t i = 0; i < n; i++) verdicts_out[i] = (st[i] & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
   return COA_OK;
+}
+
+int coa_message_resolve_raw(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins,
+                            const uint8_t* authors, const uint8_t* sigs, size_t n, uint32_t* raw) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!ids || !authors || !sigs || !raw || (rounds && !origins)) return fail(COA_EINVAL, "null argument");
+  const MsgIn in{nullptr, nullptr, ids, rounds, origins, authors, sigs, rounds != nullptr};
+  return messages_resolve(in, n, raw);
+}
+
+// k_msg_verify_lat over device arrays, on the pinned (the queue) or current
+// key-cache generation.
+static int msg_lat_launch(int device, const CoaMsgLatIn* in, uint32_t* d_status, uint32_t* d_ctr, uint32_t* host_res,
+                          uint32_t tag, void* stream) {
+  const int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!in) return fail(COA_EINVAL, "null argument");
+  const size_t n = in->nh + in->nv;
+  if (n == 0) return COA_OK;
+  if ((in->nh && (!in->hdr_data || !in->hdr_off || !in->hids || !in->hauthors || !in->hsigs)) ||
+      (in->nv && (!in->vids || !in->vrounds || !in->vorigins || !in->vauthors || !in->vsigs)) || !d_status)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(2 * n) != COA_OK) return COA_EINVAL;  // 2 nh + nv blocks
+  Dev* d = dev_by_id(device);
+  if (!d) return fail(COA_EINVAL, "device not opened by coa_init");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  MsgLatArgs a{};
+  a.hdr_data = in->hdr_data;
+  a.hdr_off = in->hdr_off;
+  a.ids = reinterpret_cast<const uint32_t*>(in->hids);
+  a.hauthors = reinterpret_cast<const uint32_t*>(in->hauthors);
+  a.hsigs = reinterpret_cast<const uint32_t*>(in->hsigs);
+  a.vids = reinterpret_cast<const uint32_t*>(in->vids);
+  a.vrounds = in->vrounds;
+  a.vorigins = reinterpret_cast<const uint32_t*>(in->vorigins);
+  a.vauthors = reinterpret_cast<const uint32_t*>(in->vauthors);
+  a.vsigs = reinterpret_cast<const uint32_t*>(in->vsigs);
+  a.nh = (uint32_t)in->nh;
+  a.nv = (uint32_t)in->nv;
+  const KeySetP ks = keys_now(*d);  // see coa_lat_verify_device
+  a.keys = ks->ckeys.as<uint32_t>();
+  a.kflags = ks->kflags.as<uint32_t>();
+  a.ktabs = ks->ktabs.as<uint32_t>();
+  a.nk = ks->nkeys;
+  a.comb = d->comb;
+  a.status = d_status;
+  if (host_res) {
+    a.host_res = host_res;
+    a.done_ctr = d_ctr;
+    a.tag = tag;
+  } else {
+    HIP_TRY(hipMemsetAsync(d_status, 0, n * 4, s));
+  }
+  HIP_TRY(coa_launch_msg_verify_lat(a, s));
+  return trail_keys(*d, ks, s);
+}
+
+int coa_msg_lat_verify_device(int device, const CoaMsgLatIn* in, uint32_t* d_status, void* stream) {
+  return msg_lat_launch(device, in, d_status, nullptr, nullptr, 0, stream);
+}
+
+int coa_msg_lat_verify_publish(int device, const CoaMsgLatIn* in, uint32_t* d_ctr, uint32_t* host_res, uint32_t tag,
+                               void* stream) {
+  if (!in || !d_ctr || !host_res || tag == 0) return fail(COA_EINVAL, "null argument or zero tag");
+  if (in->nh + in->nv > 64) return fail(COA_EINVAL, "more messages than the result words hold");
+  return msg_lat_launch(device, in, d_ctr + 1, d_ctr, host_res, tag, stream);
 }
 
 size_t coa_message_workspace_bytes(size_t n) { return coa_msg_scratch_bytes(n); }
