@@ -20,6 +20,8 @@
 //   k_build_comb     comb table: entry (j, v) = (v+1)*256^j*B, affine Niels
 //   k_halve          (k, s) -> (c, |d|, e, H, sign d)
 //   k_verify_halved  decompression + small-order checks + Q == O
+//   k_pre_halve, k_verify_main / k_verify_main2 / k_verify_main_sums
+//                    the same in two launches (the default path)
 #include "coa_halved.h"
 
 #include <atomic>
@@ -28,6 +30,7 @@
 
 #include "coa_fe.h"
 #include "coa_ge.h"
+#include "coa_ge_sums.h"
 #include "coa_halve.h"
 #include "coa_sc.h"
 #include "coa_sha512.h"
@@ -285,7 +288,9 @@ COA_DEV void load8_u4(uint32_t* dst, const void* src) {
 // The checks that do not need k (the "pre" roles of k_pre_halve), for one of
 // the item's two points: which = 0 takes A (and s < l), which = 1 takes R.
 // The point decompresses (dalek rules) and is not small order; then its
-// table j*(-P), j = 1..8, goes to table `which` of slab i.  Returns ok.
+// table j*(-P), j = 1..8, goes to table `which` of slab i (PLAIN_R: table 1
+// in tab2_form's plain-T form).  Returns ok.
+template <bool PLAIN_R>
 COA_DEV bool pre_one(const uint8_t* __restrict__ pks, const uint8_t* __restrict__ sigs, uint32_t i, uint32_t which,
                      uint32_t* __restrict__ scr) {
   uint32_t w[8], sw[8];
@@ -300,7 +305,12 @@ COA_DEV bool pre_one(const uint8_t* __restrict__ pks, const uint8_t* __restrict_
   fe_neg(Q.T, Q.T);
   // a table may be built for an item whose other point then fails: that
   // role's flag byte keeps k_verify_main from reading it
-  if (ok) tab2_build(scr, i, (int)which, Q);
+  if (ok) {
+    if constexpr (PLAIN_R)
+      tab2_build_form(scr, i, (int)which, Q, which != 0);
+    else
+      tab2_build(scr, i, (int)which, Q);
+  }
   return ok;
 }
 }  // namespace
@@ -321,7 +331,8 @@ __global__ void __launch_bounds__(256) k_halve(const uint32_t* __restrict__ kbuf
 // each other's gaps (a lone wave issues a VALU instruction at most every ~4
 // cycles), and the latency-bound halving (f64 quotient chains) and the hash
 // fill what is left.  flags[2i + which] is the A / R role's pre-check.
-template <int WAVES>
+// PLAIN_R: table 1 (R) in the plain-T form that k_verify_main_sums reads.
+template <int WAVES, bool PLAIN_R>
 __global__ void __launch_bounds__(256, WAVES) k_pre_halve(const uint8_t* __restrict__ pks,
                                                       const uint8_t* __restrict__ sigs,
                                                       const uint8_t* __restrict__ msgs, uint32_t msg_len,
@@ -335,7 +346,7 @@ __global__ void __launch_bounds__(256, WAVES) k_pre_halve(const uint8_t* __restr
     if (prio & 2) return;  // diagnostic (COA_PRE_DIAG): time the hash role alone
     const uint32_t which = blockIdx.x >= pre_blocks ? 1u : 0u;
     const uint32_t i = (blockIdx.x - which * pre_blocks) * blockDim.x + threadIdx.x;
-    if (i < n) flags[2 * i + which] = pre_one(pks, sigs, i, which, scr) ? 1 : 0;
+    if (i < n) flags[2 * i + which] = pre_one<PLAIN_R>(pks, sigs, i, which, scr) ? 1 : 0;
     return;
   }
   const uint32_t i = (blockIdx.x - 2 * pre_blocks) * blockDim.x + threadIdx.x;
@@ -647,6 +658,152 @@ __global__ void __launch_bounds__(128, 2) k_verify_main2(const uint32_t* __restr
   if (live) verdicts[i] = verdict;
 }
 
+// Split verification, phase 2 with each digit's table sum in a second wave:
+// S_pos = A_tab[dc] + R_tab[dr] depends on neither the accumulator nor the
+// other digits, so of a workgroup's eight waves (256 items; a 512-lane
+// workgroup puts waves k and k + 4 on SIMD k) waves 4-7, the producers,
+// compute S_pos one digit ahead of waves 0-3, the consumers, which keep the
+// accumulator and do four doublings and one addition per digit.  The
+// doublings stay single; the producer's p1p1 -> p3 -> cached costs one
+// product more per digit than k_verify_main's second p1p1 -> p3.  Table 1 is
+// in tab2_form's plain-T form (coa_ge_sums.h, ge_add_cc_il).  S passes through
+// two LDS slots of [dword][item]: in iteration pos the consumer reads slot
+// pos & 1 while the producer writes digit pos - 1 into the other, then one
+// barrier.
+// Every wave of the workgroup executes the same barriers: H is the maximum
+// over all eight waves (through LDS), dead lanes and rejected items run the
+// loop with zero digits (their loads then read tab2_identity only), and no
+// wave returns before the loop ends.
+// PRIO: 0 none; 1 / 2 raise the consumers' / the producers' wave priority.
+// SWAP: the producers are waves 0-3, the older ones.  Both are A/B builds
+// only (-DCOA_SUMS_PRIO / -DCOA_SUMS_SWAP); each measured no better than the
+// plain form (profiles/r08_main_sums_ab.txt).
+#ifndef COA_SUMS_PRIO
+#define COA_SUMS_PRIO 0
+#endif
+#ifndef COA_SUMS_SWAP
+#define COA_SUMS_SWAP 0
+#endif
+template <int PRIO, bool SWAP>
+__global__ void __launch_bounds__(512) k_verify_main_sums(const uint32_t* __restrict__ rec,
+                                                          const uint8_t* __restrict__ flags, uint32_t n,
+                                                          uint8_t* __restrict__ verdicts,
+                                                          const uint32_t* __restrict__ scr,
+                                                          const uint32_t* __restrict__ ebp) {
+  __shared__ uint32_t s_lds[2][32][256];  // 64 KiB; the H exchange borrows s_lds[0][0][0..7] first
+  const uint32_t slot_item = threadIdx.x & 255u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
+  const bool producer = SWAP ? wave < 4 : wave >= 4;
+  const uint32_t i = blockIdx.x * 256u + slot_item;
+  const bool live = i < n;
+  const uint32_t ii = live ? i : 0u;  // every load below is in bounds
+  const uint32_t* myrec = rec + (uint64_t)ii * 32;
+  const uint16_t fl = reinterpret_cast<const uint16_t*>(flags)[ii];
+  const uint32_t meta0 = myrec[24];
+  const bool ok = live && fl == 0x0101u;
+  const uint32_t meta = ok ? meta0 : 0u;
+  // H over the whole workgroup, so that all eight waves loop equally often
+  const int hw = wave_max((int)(meta & 0xffu));
+  if ((threadIdx.x & 63u) == 0) s_lds[0][0][wave] = (uint32_t)hw;
+  __syncthreads();
+  int H = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) H = max(H, (int)s_lds[0][0][w]);
+  H = __builtin_amdgcn_readfirstlane(H);
+  __syncthreads();  // the exchange words are read before the first sum overwrites them
+  if constexpr (PRIO != 0) {
+    if (producer == (PRIO == 2)) __builtin_amdgcn_s_setprio(2);
+  }
+  // From here each role has its own loop, so that neither's registers stay
+  // live through the other's code.  `producer` and H are wave-uniform scalars,
+  // and both roles execute exactly 1 + H barriers below: one in front of the
+  // loop and one at the end of each of its H iterations, none under a
+  // per-lane condition.
+  if (producer) {
+    uint32_t cw[8], dw[8];  // the digit words
+    load8_u4(cw, myrec);
+    load8_u4(dw, myrec + 8);
+    if (!ok) {  // zero digits: such a lane adds the identity at every position
+#pragma unroll
+      for (int j = 0; j < 8; j++) cw[j] = dw[j] = 0x88888888u;
+    }
+    const bool dneg = (meta >> 31) != 0;
+    auto produce = [&](int pos) {  // S_pos into slot pos & 1
+      const int sh = 4 * (pos & 7);
+      const int dc = (int)((cw[pos >> 3] >> sh) & 15u) - 8;
+      const int dd = (int)((dw[pos >> 3] >> sh) & 15u) - 8;
+      const int dr = dneg ? -dd : dd;
+      ge_cached qa, qr, c;
+      tab2_load(qa, scr, i, 0, dc);
+      tab2_load(qr, scr, i, 1, dr);
+      ge_p1p1 u;
+      ge_p3 s3;
+      ge_add_cc_il(u, qa, qr, (dc < 0) != (dr < 0));
+      ge_p1p1_to_p3_il(s3, u);
+      ge_p3_to_cached(c, s3);
+      const fe* f[4] = {&c.YplusX, &c.YminusX, &c.Z, &c.T2d};
+#pragma unroll
+      for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int k = 0; k < 8; k++) s_lds[pos & 1][8 * q + k][slot_item] = f[q]->v[k];
+    };
+    if (H > 0) produce(H - 1);
+    __syncthreads();
+#pragma unroll 1
+    for (int pos = H - 1; pos >= 0; pos--) {
+      if (pos > 0) produce(pos - 1);
+      __syncthreads();
+    }
+    return;  // after the last barrier
+  }
+  ge_p3 acc3;
+  ge_p2 acc2;
+  ge_p1p1 t;
+  ge_p3_identity(acc3);
+  // p1p1 form of the identity: what the tail converts when H == 0
+  fe_set(t.X, 0);
+  fe_set(t.Y, 1);
+  fe_set(t.Z, 1);
+  fe_set(t.T, 1);
+  __syncthreads();
+#pragma unroll 1
+  for (int pos = H - 1; pos >= 0; pos--) {
+    ge_cached sq;
+    fe* f[4] = {&sq.YplusX, &sq.YminusX, &sq.Z, &sq.T2d};
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+      for (int k = 0; k < 8; k++) f[q]->v[k] = s_lds[pos & 1][8 * q + k][slot_item];
+    if (pos != H - 1) {
+#pragma unroll 1
+      for (int k = 0; k < 3; k++) {
+        ge_p2_dbl_il(t, acc2);
+        ge_p1p1_to_p2_il(acc2, t);
+      }
+      ge_p2_dbl_il(t, acc2);
+      ge_p1p1_to_p3_il(acc3, t);
+    }
+    ge_add_il(t, acc3, sq);
+    if (pos != 0) ge_p1p1_to_p2_il(acc2, t);
+    __syncthreads();
+  }
+  uint8_t verdict = 1;
+  if (ok) {
+    ge_p1p1_to_p3_il(acc3, t);
+    // + [e]B, computed by the halving role
+    ge_cached eb;
+    fe* fb[4] = {&eb.YplusX, &eb.YminusX, &eb.Z, &eb.T2d};
+#pragma unroll
+    for (int q = 0; q < 4; q++) load8_u4(fb[q]->v, ebp + (uint64_t)i * 32 + 8 * q);
+    ge_add(t, acc3, eb);
+    ge_p1p1_to_p3(acc3, t);
+    ge_p2 q2;
+    ge_p3_to_p2(q2, acc3);
+    verdict = ge_p2_is_identity(q2) ? 0 : 1;
+  }
+  if (live) verdicts[i] = verdict;
+}
+
 template <int WAVES>
 __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __restrict__ pks,
                                                           const uint8_t* __restrict__ sigs,
@@ -832,10 +989,6 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
                           | (getenv("COA_PRE_DIAG") ? atoi(getenv("COA_PRE_DIAG")) & 6 : 0)
 #endif
       ;
-  hipLaunchKernelGGL(k_pre_halve<3>, dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned, kbuf, n,
-                     rec, flags, scratch, ebp, comb, wcomb, blocks, prio);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
   // at most one wave per SIMD (65,536 items on the 256 CUs of an MI355X, the
   // C2 size): the interleaved formulas; COA_MAIN_IL=0/1 forces either (A/B)
   const char* il_env = getenv("COA_MAIN_IL");
@@ -851,8 +1004,30 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   // A/B of COA_MAIN_IL alone never measures k_verify_main2 instead.
   const char* two_s = getenv("COA_MAIN_TWO");
   const int two_env = two_s ? atoi(two_s) : (il_env ? 0 : -1);
-  const bool two = ebp && (two_env >= 0 ? two_env != 0 : 4ull * n <= one_wave_per_simd_items());
-  if (two)
+  // each digit's table sum in a second wave (k_verify_main_sums): above
+  // k_verify_main2's sizes and up to one wave per SIMD, where the one-lane
+  // kernel leaves half of every SIMD's issue slots idle.  COA_MAIN_SUMS=0/1
+  // forces either at every size (A/B; 1 goes before COA_MAIN_TWO); an
+  // explicit COA_MAIN_IL or COA_MAIN_TWO without it keeps selecting the
+  // kernels those name.
+  const char* sums_s = getenv("COA_MAIN_SUMS");
+  const int sums_env = sums_s ? atoi(sums_s) : ((il_env || two_s) ? 0 : -1);
+  const bool sums = ebp && (sums_env >= 0 ? sums_env != 0
+                                          : 4ull * n > one_wave_per_simd_items() && n <= one_wave_per_simd_items());
+  const bool two = ebp && !sums && (two_env >= 0 ? two_env != 0 : 4ull * n <= one_wave_per_simd_items());
+  // phase 1 stores table 1 in the form the main kernel launched below reads
+  if (sums)
+    hipLaunchKernelGGL((k_pre_halve<3, true>), dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned,
+                       kbuf, n, rec, flags, scratch, ebp, comb, wcomb, blocks, prio);
+  else
+    hipLaunchKernelGGL((k_pre_halve<3, false>), dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned,
+                       kbuf, n, rec, flags, scratch, ebp, comb, wcomb, blocks, prio);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (sums)
+    hipLaunchKernelGGL((k_verify_main_sums<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512), 0, s,
+                       rec, flags, n, verdicts, scratch, ebp);
+  else if (two)
     hipLaunchKernelGGL(k_verify_main2, dim3((n + 63) / 64), dim3(128), 0, s, rec, flags, n, verdicts, scratch, ebp);
   else if (il)
     hipLaunchKernelGGL((k_verify_main<1, true>), dim3((n + main_b - 1) / main_b), dim3(main_b), 0, s, rec, flags, n,
