@@ -207,8 +207,9 @@ int coa_committee_key_flags(uint32_t* flags_out, size_t cap);
  *                            votes) fails (messages.rs:214; the digest is
  *                            SHA-512(id || round u64 LE || origin)[..32],
  *                            messages.rs:226-234, computed on the device)
- * The non-crypto checks (genesis, stake, worker ids, quorum) stay with the
- * caller, which applies them in the reference's order with these bits
+ * These calls leave the non-crypto checks (genesis, stake, worker ids,
+ * quorum) to the caller, which applies them in the reference's order with
+ * these bits; coa_certificate_verdict_many below decides them too
  * (INTEGRATION.md).  Votes are checked per signature with the committee
  * combs; when every vote holds its own cofactorless equation and every key is
  * torsion free, dalek's batch verdict is Ok for any weights.  Any other
@@ -292,6 +293,101 @@ int coa_header_verify_many_device(int device, const uint8_t* d_header_data, cons
 int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
                                 const uint8_t* d_authors, const uint8_t* d_sigs, size_t n, uint32_t* d_status,
                                 void* workspace, void* stream);
+
+/* ------------- Certificate::verify / Header::verify / Vote::verify verdicts
+ * The whole of Certificate::verify (primary/src/messages.rs:189-215),
+ * Header::verify (:48-67) and Vote::verify (:131-142) decided by the engine:
+ * the crypto bits of the calls above merged on the device with the protocol
+ * checks (genesis, stake, worker ids, reuse, quorum) in the reference's
+ * order, so a caller gets the reference's DagResult as one word per item
+ * instead of interleaving bits and checks itself.
+ *
+ * coa_committee_register_authorities mirrors config::Committee
+ * (config/src/lib.rs:130-143; Stake and WorkerId are u32): authority i has
+ * key pks[32 i ..], stake stakes[i] and the worker ids
+ * worker_ids[worker_offsets[i] .. worker_offsets[i+1]).  It does everything
+ * coa_committee_register does and builds, in the same key-cache generation,
+ * the protocol table the verdict calls read: stakes and sorted worker ids in
+ * the engine's key order, and quorum = 2 * total / 3 + 1
+ * (Committee::quorum_threshold, config/src/lib.rs:168-173).  A call or queue
+ * window that pinned a generation reads that generation's stakes.  Rejected
+ * with COA_EINVAL (text in coa_last_error): duplicate keys (a BTreeMap holds
+ * none), a total stake of 2^31 or more (the reference's 2 * total_votes
+ * overflows there), more than COA_MAX_AUTHORITIES keys (the reuse table of
+ * the certificate kernel is COA_MAX_AUTHORITIES words of LDS per wavefront).
+ * Stake 0 is legal: the key is cached, and the reference answers
+ * UnknownAuthority for it.  Returns the number of keys or a negative error.
+ * After plain coa_committee_register the generation has no protocol table
+ * and the verdict calls return COA_EINVAL. */
+#define COA_MAX_AUTHORITIES 1024
+int coa_committee_register_authorities(const uint8_t* pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                       const uint64_t* worker_offsets, size_t n);
+/* A verdict is a uint32_t: bits 0-7 the code, the first check of the
+ * reference that fails; for COA_DAG_AUTHORITY_REUSE and COA_DAG_UNKNOWN_VOTER
+ * bits 8-31 hold the index of the offending vote within its certificate (the
+ * key the reference's error names). */
+#define COA_DAG_OK 0                /* Ok; also genesis, messages.rs:190-193 */
+#define COA_DAG_INVALID_HEADER_ID 1 /* messages.rs:50 */
+#define COA_DAG_UNKNOWN_AUTHOR 2    /* :53-54, :133-136: the author's stake is 0 */
+#define COA_DAG_MALFORMED_HEADER 3  /* :57-61: a worker id the author does not have */
+#define COA_DAG_INVALID_SIGNATURE 4 /* :64-66, :139-141 */
+#define COA_DAG_AUTHORITY_REUSE 5   /* :202 */
+#define COA_DAG_UNKNOWN_VOTER 6     /* :203-204 */
+#define COA_DAG_REQUIRES_QUORUM 7   /* :208-211 */
+#define COA_DAG_INVALID_VOTES 8     /* :214 */
+#define COA_DAG_VOTES_OPEN 9        /* device-resident form only: every earlier check passed and the votes need
+                                       the exact check (coa_ed25519_verify_batch_groups), as raw status bit 8 */
+#define COA_DAG_CODE(v) ((v) & 0xffu)
+#define COA_DAG_VOTE_INDEX(v) ((v) >> 8)
+/* Semantics, exactly the reference's:
+ *   - genesis (:190-193): id is 32 zero bytes, round 0 and origin a MEMBER of
+ *     the committee, whatever its stake (Certificate::genesis iterates
+ *     authorities.keys(); PartialEq, :249-256, compares id, round and origin
+ *     only) is COA_DAG_OK whatever else the certificate holds;
+ *   - the vote loop (:201-207) reports the first failing vote in vote order,
+ *     reuse tested before stake at each vote; the weight is summed in 64 bits;
+ *   - worker id k of a header is the u32 LE at byte 40 + 36 k + 32 of its
+ *     digest input; payload_counts[i] (what the wire decoders fill) is the
+ *     number of payload entries.  A count that overruns its header is
+ *     COA_EINVAL for a host-pointer call; the device-resident forms, which
+ *     cannot see it before they return, answer COA_DAG_MALFORMED_HEADER.
+ * Host-pointer forms: the arguments of coa_certificate_verify_many /
+ * coa_header_verify_many / coa_vote_verify_many plus payload_counts; sharded
+ * by index range like them.  COA_DAG_VOTES_OPEN is resolved through the exact
+ * path (rng_seed as there); nothing else goes to a resolver: an item whose
+ * author or voter is outside the committee is answered by the protocol word
+ * alone. */
+int coa_certificate_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                 const uint8_t* origins, const uint8_t* header_sigs, const uint64_t* rounds,
+                                 const uint8_t* vote_pks, const uint8_t* vote_sigs, const uint64_t* vote_offsets,
+                                 size_t n, uint64_t rng_seed, const uint32_t* payload_counts,
+                                 uint32_t* verdicts_out);
+int coa_header_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                            const uint8_t* authors, const uint8_t* sigs, size_t n, const uint32_t* payload_counts,
+                            uint32_t* verdicts_out);
+int coa_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                          const uint8_t* sigs, size_t n, uint32_t* verdicts_out);
+/* Device-resident forms (asynchronous on `stream`; NULL = the engine's
+ * stream): the crypto launch of the *_verify_many_device call, the protocol
+ * kernel and the merge, all on `stream`.  d_verdicts[c] may hold
+ * COA_DAG_VOTES_OPEN.  `workspace`: NULL (engine-owned; the call then waits
+ * for its stream) or at least coa_*_verdict_workspace_bytes bytes of device
+ * memory (the crypto call's workspace plus two words per item). */
+size_t coa_certificate_verdict_workspace_bytes(size_t n, size_t n_votes);
+int coa_certificate_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                        const uint8_t* d_ids, const uint8_t* d_origins, const uint8_t* d_header_sigs,
+                                        const uint64_t* d_rounds, const uint8_t* d_vote_pks,
+                                        const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
+                                        size_t n_votes, const uint32_t* d_payload_counts, uint32_t* d_verdicts,
+                                        void* workspace, void* stream);
+size_t coa_message_verdict_workspace_bytes(size_t n);
+int coa_header_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                   const uint8_t* d_ids, const uint8_t* d_authors, const uint8_t* d_sigs, size_t n,
+                                   const uint32_t* d_payload_counts, uint32_t* d_verdicts, void* workspace,
+                                   void* stream);
+int coa_vote_verdict_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
+                                 const uint8_t* d_authors, const uint8_t* d_sigs, size_t n, uint32_t* d_verdicts,
+                                 void* workspace, void* stream);
 
 /* ------------------------------------------------------- wire decode (f4)
  * bincode 1.3 decode of PrimaryMessage frames, as
@@ -384,6 +480,40 @@ int coa_cpu_header_verify_many(const uint8_t* header_data, const uint64_t* heade
                                int nthreads);
 int coa_cpu_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
                              const uint8_t* sigs, size_t n, uint8_t* verdicts_out, int nthreads);
+/* The verdict calls on the CPU path: COA_DAG_* words, never
+ * COA_DAG_VOTES_OPEN.  Stateless like the calls above: the committee arrays
+ * of coa_committee_register_authorities are passed in each call and rejected
+ * by the same rules.
+ *   coa_cpu_certificate_verdict_many   primary/src/messages.rs:189-215
+ *   coa_cpu_header_verdict_many        primary/src/messages.rs:48-67
+ *   coa_cpu_vote_verdict_many          primary/src/messages.rs:131-142
+ *   coa_cpu_certificate_verdict_from_status  the protocol checks and the merge
+ *                                      alone, for a caller that holds the
+ *                                      COA_CERT_* bits of each certificate
+ *                                      (status: n bytes) */
+int coa_cpu_certificate_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                     const uint8_t* origins, const uint8_t* header_sigs, const uint64_t* rounds,
+                                     const uint8_t* vote_pks, const uint8_t* vote_sigs, const uint64_t* vote_offsets,
+                                     size_t n, uint64_t rng_seed, const uint32_t* payload_counts,
+                                     const uint8_t* committee_pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                     const uint64_t* worker_offsets, size_t n_authorities, uint32_t* verdicts_out,
+                                     int nthreads);
+int coa_cpu_certificate_verdict_from_status(const uint8_t* header_data, const uint64_t* header_offsets,
+                                            const uint8_t* ids, const uint8_t* origins, const uint64_t* rounds,
+                                            const uint8_t* vote_pks, const uint64_t* vote_offsets, size_t n,
+                                            const uint32_t* payload_counts, const uint8_t* status,
+                                            const uint8_t* committee_pks, const uint32_t* stakes,
+                                            const uint32_t* worker_ids, const uint64_t* worker_offsets,
+                                            size_t n_authorities, uint32_t* verdicts_out, int nthreads);
+int coa_cpu_header_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                const uint8_t* authors, const uint8_t* sigs, size_t n, const uint32_t* payload_counts,
+                                const uint8_t* committee_pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                const uint64_t* worker_offsets, size_t n_authorities, uint32_t* verdicts_out,
+                                int nthreads);
+int coa_cpu_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins,
+                              const uint8_t* authors, const uint8_t* sigs, size_t n, const uint8_t* committee_pks,
+                              const uint32_t* stakes, const uint32_t* worker_ids, const uint64_t* worker_offsets,
+                              size_t n_authorities, uint32_t* verdicts_out, int nthreads);
 
 /* ------------------------------------------------ aggregation queue (f1)
  * Pre-verification stage for Core::run (primary/src/core.rs:349-389), which

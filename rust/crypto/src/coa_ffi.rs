@@ -21,6 +21,20 @@ pub const COA_CERT_BAD_HEADER_ID: c_int = 1;
 pub const COA_CERT_BAD_HEADER_SIG: c_int = 2;
 pub const COA_CERT_BAD_VOTES: c_int = 4;
 
+/// Verdict words (coa_*_verdict_many): the code in bits 0-7, the index of the
+/// offending vote in bits 8-31 for AUTHORITY_REUSE and UNKNOWN_VOTER.
+pub const COA_MAX_AUTHORITIES: usize = 1024;
+pub const COA_DAG_OK: u32 = 0;
+pub const COA_DAG_INVALID_HEADER_ID: u32 = 1;
+pub const COA_DAG_UNKNOWN_AUTHOR: u32 = 2;
+pub const COA_DAG_MALFORMED_HEADER: u32 = 3;
+pub const COA_DAG_INVALID_SIGNATURE: u32 = 4;
+pub const COA_DAG_AUTHORITY_REUSE: u32 = 5;
+pub const COA_DAG_UNKNOWN_VOTER: u32 = 6;
+pub const COA_DAG_REQUIRES_QUORUM: u32 = 7;
+pub const COA_DAG_INVALID_VOTES: u32 = 8;
+pub const COA_DAG_VOTES_OPEN: u32 = 9;
+
 pub const COA_MSG_HEADER: i32 = 0;
 pub const COA_MSG_VOTE: i32 = 1;
 pub const COA_MSG_CERTIFICATE: i32 = 2;
@@ -166,6 +180,39 @@ extern "C" {
                                        d_status: *mut u32, workspace: *mut c_void,
                                        stream: *mut c_void) -> c_int;
 
+    // ---------- Certificate::verify / Header::verify / Vote::verify verdicts
+    // COA_DAG_* words: the protocol checks decided by the engine too
+    pub fn coa_committee_register_authorities(pks: *const u8, stakes: *const u32, worker_ids: *const u32,
+                                              worker_offsets: *const u64, n: usize) -> c_int;
+    pub fn coa_certificate_verdict_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                        origins: *const u8, header_sigs: *const u8, rounds: *const u64,
+                                        vote_pks: *const u8, vote_sigs: *const u8, vote_offsets: *const u64,
+                                        n: usize, rng_seed: u64, payload_counts: *const u32,
+                                        verdicts_out: *mut u32) -> c_int;
+    pub fn coa_header_verdict_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                   authors: *const u8, sigs: *const u8, n: usize, payload_counts: *const u32,
+                                   verdicts_out: *mut u32) -> c_int;
+    pub fn coa_vote_verdict_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
+                                 sigs: *const u8, n: usize, verdicts_out: *mut u32) -> c_int;
+    pub fn coa_certificate_verdict_workspace_bytes(n: usize, n_votes: usize) -> usize;
+    pub fn coa_certificate_verdict_many_device(device: c_int, d_header_data: *const u8,
+                                               d_header_offsets: *const u64, d_ids: *const u8,
+                                               d_origins: *const u8, d_header_sigs: *const u8,
+                                               d_rounds: *const u64, d_vote_pks: *const u8,
+                                               d_vote_sigs: *const u8, d_vote_offsets: *const u64, n: usize,
+                                               n_votes: usize, d_payload_counts: *const u32,
+                                               d_verdicts: *mut u32, workspace: *mut c_void,
+                                               stream: *mut c_void) -> c_int;
+    pub fn coa_message_verdict_workspace_bytes(n: usize) -> usize;
+    pub fn coa_header_verdict_many_device(device: c_int, d_header_data: *const u8, d_header_offsets: *const u64,
+                                          d_ids: *const u8, d_authors: *const u8, d_sigs: *const u8, n: usize,
+                                          d_payload_counts: *const u32, d_verdicts: *mut u32,
+                                          workspace: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn coa_vote_verdict_many_device(device: c_int, d_ids: *const u8, d_rounds: *const u64,
+                                        d_origins: *const u8, d_authors: *const u8, d_sigs: *const u8, n: usize,
+                                        d_verdicts: *mut u32, workspace: *mut c_void,
+                                        stream: *mut c_void) -> c_int;
+
     // --------------------------------------------------- wire decode (f4)
     pub fn coa_wire_scan(frames: *const u8, frame_offsets: *const u64, n: usize, kind_out: *mut i32,
                          header_bytes_out: *mut u64, votes_out: *mut u64) -> c_int;
@@ -214,6 +261,32 @@ extern "C" {
                                       nthreads: c_int) -> c_int;
     pub fn coa_cpu_vote_verify_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
                                     sigs: *const u8, n: usize, verdicts_out: *mut u8, nthreads: c_int) -> c_int;
+    // the verdict calls on the CPU path (stateless: the committee arrays in each call)
+    pub fn coa_cpu_certificate_verdict_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                            origins: *const u8, header_sigs: *const u8, rounds: *const u64,
+                                            vote_pks: *const u8, vote_sigs: *const u8,
+                                            vote_offsets: *const u64, n: usize, rng_seed: u64,
+                                            payload_counts: *const u32, committee_pks: *const u8,
+                                            stakes: *const u32, worker_ids: *const u32,
+                                            worker_offsets: *const u64, n_authorities: usize,
+                                            verdicts_out: *mut u32, nthreads: c_int) -> c_int;
+    pub fn coa_cpu_certificate_verdict_from_status(header_data: *const u8, header_offsets: *const u64,
+                                                   ids: *const u8, origins: *const u8, rounds: *const u64,
+                                                   vote_pks: *const u8, vote_offsets: *const u64, n: usize,
+                                                   payload_counts: *const u32, status: *const u8,
+                                                   committee_pks: *const u8, stakes: *const u32,
+                                                   worker_ids: *const u32, worker_offsets: *const u64,
+                                                   n_authorities: usize, verdicts_out: *mut u32,
+                                                   nthreads: c_int) -> c_int;
+    pub fn coa_cpu_header_verdict_many(header_data: *const u8, header_offsets: *const u64, ids: *const u8,
+                                       authors: *const u8, sigs: *const u8, n: usize,
+                                       payload_counts: *const u32, committee_pks: *const u8, stakes: *const u32,
+                                       worker_ids: *const u32, worker_offsets: *const u64, n_authorities: usize,
+                                       verdicts_out: *mut u32, nthreads: c_int) -> c_int;
+    pub fn coa_cpu_vote_verdict_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
+                                     sigs: *const u8, n: usize, committee_pks: *const u8, stakes: *const u32,
+                                     worker_ids: *const u32, worker_offsets: *const u64, n_authorities: usize,
+                                     verdicts_out: *mut u32, nthreads: c_int) -> c_int;
 
     // ------------------------------------------------- aggregation queue (f1)
     pub fn coa_queue_create(max_batch: usize, max_delay_us: u32) -> *mut CoaQueue;

@@ -129,6 +129,30 @@ fn checks_in_order(cert: &Certificate, committee: &Committee, st: c_int) -> DagR
     Ok(())
 }
 
+/// The DagResult of one verdict word of `coa_certificate_verdict_many`
+/// (include/coa_verify.h, COA_DAG_*): the engine has applied every check of
+/// Certificate::verify in the reference's order on the device, protocol
+/// checks included (`coa_committee_register_authorities`), so nothing is
+/// looked up here but the key the reference's error names.  Beside
+/// `checks_in_order`, which `verify` and `verify_many` still use.
+pub fn verdict_to_dag_error(word: u32, cert: &Certificate) -> DagResult<()> {
+    let h = &cert.header;
+    let vote = (word >> 8) as usize;
+    match word & 0xff {
+        0 => Ok(()),                                                   // COA_DAG_OK (also genesis, :190-193)
+        1 => Err(DagError::InvalidHeaderId),                           // :50
+        2 => Err(DagError::UnknownAuthority(h.author)),                // :53-54
+        3 => Err(DagError::MalformedHeader(h.id.clone())),             // :57-61
+        4 | 8 => Err(DagError::InvalidSignature(CryptoError::new())),  // :64-66, :214
+        5 => Err(DagError::AuthorityReuse(cert.votes[vote].0)),        // :202
+        6 => Err(DagError::UnknownAuthority(cert.votes[vote].0)),      // :203-204
+        7 => Err(DagError::CertificateRequiresQuorum),                 // :208-211
+        // COA_DAG_VOTES_OPEN is the device-resident form's alone; the
+        // host-pointer call resolves it before it returns
+        code => panic!("unexpected verdict code {} from the engine", code),
+    }
+}
+
 /// Certificate::verify, one certificate: the bits the pre-verification
 /// stage computed for exactly these bytes, or the engine's latency path (one
 /// launch with the certificate in its arguments, on an idle device context).

@@ -19,6 +19,9 @@ host-side protocol checks, so the error raised is the reference's.
 certificates with one coa_certificate_verify_many call; `verify_headers` /
 `verify_votes` do it for a backlog of Header / Vote messages with one
 coa_header_verify_many / coa_vote_verify_many call each.
+`verdict_certificates` / `verdict_headers` / `verdict_votes` return the same
+errors from the engine's verdict calls (the protocol checks on the device
+too, after `Committee.register_authorities()`): no per-item check on the host.
 """
 import struct
 
@@ -81,6 +84,15 @@ class Committee:
         """Hand the committee's keys to the engine's key cache (f2).  Needed
         for speed only: verdicts do not depend on it."""
         return coa_crypto.committee_register(np.array([list(bytes(k)) for k in self.authorities()], np.uint8))
+
+    def register_authorities(self):
+        """Hand the whole committee -- keys, stakes and worker ids -- to the
+        engine (coa_committee_register_authorities): what `register` does, plus
+        the protocol table the verdict_* functions below need."""
+        names = self.authorities()
+        return coa_crypto.committee_register_authorities(
+            np.array([list(bytes(k)) for k in names], np.uint8).reshape(-1, 32), [self.stakes[k] for k in names],
+            [sorted(self.workers.get(k, {0})) for k in names])
 
 
 class Header:
@@ -302,6 +314,88 @@ def verify_votes(votes, committee):
         elif verdicts[i]:                                           # :139-141
             res[i] = InvalidSignature()
     return res
+
+
+# ---------------------------------------------------------------------------
+# The same answers from the engine's verdict calls: the protocol checks run on
+# the device beside the crypto (Committee.register_authorities), and the host
+# only maps each COA_DAG_* word to the error the reference raises.
+def _dag_error(word, header=None, votes=None, author=None):
+    code, idx = int(word) & 0xff, int(word) >> 8
+    if code == coa_crypto.DAG_OK:
+        return None
+    if code == coa_crypto.DAG_INVALID_HEADER_ID:                    # messages.rs:50
+        return InvalidHeaderId(header.id)
+    if code == coa_crypto.DAG_UNKNOWN_AUTHOR:                       # :53-54, :133-136
+        return UnknownAuthority(author)
+    if code == coa_crypto.DAG_MALFORMED_HEADER:                     # :57-61
+        return MalformedHeader(header.id)
+    if code == coa_crypto.DAG_AUTHORITY_REUSE:                      # :202
+        return AuthorityReuse(votes[idx][0])
+    if code == coa_crypto.DAG_UNKNOWN_VOTER:                        # :203-204
+        return UnknownAuthority(votes[idx][0])
+    if code == coa_crypto.DAG_REQUIRES_QUORUM:                      # :208-211
+        return CertificateRequiresQuorum()
+    if code in (coa_crypto.DAG_INVALID_SIGNATURE, coa_crypto.DAG_INVALID_VOTES):  # :64-66, :139-141, :214
+        return InvalidSignature()
+    raise coa_crypto.EngineError(f"unexpected verdict word {int(word):#x}")
+
+
+def verdict_certificates(certs, committee=None, rng_seed=0, cpu=False):
+    """verify_certificates' answers from ONE coa_certificate_verdict_many
+    call (the registered committee's stakes and worker ids; `committee` is
+    read only by the CPU form, cpu=True)."""
+    if not certs:
+        return []
+    hs = [c.header for c in certs]
+    ids = np.array([list(bytes(h.id)) for h in hs], np.uint8)
+    origins = np.array([list(bytes(h.author)) for h in hs], np.uint8)
+    hsigs = np.array([list(h.signature.flatten()) for h in hs], np.uint8)
+    rounds = np.array([h.round for h in hs], np.uint64)
+    vp = np.array([list(bytes(pk)) for c in certs for pk, _ in c.votes], np.uint8).reshape(-1, 32)
+    vs = np.array([list(sg.flatten()) for c in certs for _, sg in c.votes], np.uint8).reshape(-1, 64)
+    offs = np.zeros(len(certs) + 1, np.uint64)
+    offs[1:] = np.cumsum([len(c.votes) for c in certs])
+    args = ([h.digest_input() for h in hs], ids, origins, hsigs, rounds, vp, vs, offs, [len(h.payload) for h in hs])
+    if cpu:
+        words = coa_crypto.cpu_certificate_verdict_many(*args, _committee_tuple(committee), rng_seed=rng_seed)
+    else:
+        words = coa_crypto.certificate_verdict_many(*args, rng_seed=rng_seed)
+    return [_dag_error(w, c.header, c.votes, c.header.author) for w, c in zip(words, certs)]
+
+
+def verdict_headers(headers, committee=None, cpu=False):
+    """verify_headers' answers from one coa_header_verdict_many call."""
+    if not headers:
+        return []
+    ids = np.array([list(bytes(h.id)) for h in headers], np.uint8)
+    authors = np.array([list(bytes(h.author)) for h in headers], np.uint8)
+    sigs = np.array([list(h.signature.flatten()) for h in headers], np.uint8)
+    args = ([h.digest_input() for h in headers], ids, authors, sigs, [len(h.payload) for h in headers])
+    words = (coa_crypto.cpu_header_verdict_many(*args, _committee_tuple(committee)) if cpu
+             else coa_crypto.header_verdict_many(*args))
+    return [_dag_error(w, h, None, h.author) for w, h in zip(words, headers)]
+
+
+def verdict_votes(votes, committee=None, cpu=False):
+    """verify_votes' answers from one coa_vote_verdict_many call."""
+    if not votes:
+        return []
+    ids = np.array([list(bytes(v.id)) for v in votes], np.uint8)
+    origins = np.array([list(bytes(v.origin)) for v in votes], np.uint8)
+    authors = np.array([list(bytes(v.author)) for v in votes], np.uint8)
+    sigs = np.array([list(v.signature.flatten()) for v in votes], np.uint8)
+    rounds = np.array([v.round for v in votes], np.uint64)
+    args = (ids, rounds, origins, authors, sigs)
+    words = (coa_crypto.cpu_vote_verdict_many(*args, _committee_tuple(committee)) if cpu
+             else coa_crypto.vote_verdict_many(*args))
+    return [_dag_error(w, None, None, v.author) for w, v in zip(words, votes)]
+
+
+def _committee_tuple(committee):
+    names = committee.authorities()
+    return (np.array([list(bytes(k)) for k in names], np.uint8).reshape(-1, 32), [committee.stakes[k] for k in names],
+            [sorted(committee.workers.get(k, {0})) for k in names])
 
 
 # ---------------------------------------------------------------------------

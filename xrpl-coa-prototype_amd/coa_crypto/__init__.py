@@ -160,6 +160,25 @@ def lib():
                                              ctypes.c_int], ctypes.c_int),
         "coa_cpu_certificate_verify_many_z": ([P8, P64, P8, P8, P8, P64, P8, P8, P64, sz, P8, P8, ctypes.c_int],
                                               ctypes.c_int),
+        # verdicts (COA_DAG_* words): committee arrays = pks, stakes, worker ids, worker offsets, n
+        "coa_committee_register_authorities": ([P8, vp, vp, P64, sz], ctypes.c_int),
+        "coa_certificate_verdict_many": ([P8, P64, P8, P8, P8, P64, P8, P8, P64, sz, ctypes.c_uint64, vp, vp],
+                                         ctypes.c_int),
+        "coa_header_verdict_many": ([P8, P64, P8, P8, P8, sz, vp, vp], ctypes.c_int),
+        "coa_vote_verdict_many": ([P8, P64, P8, P8, P8, sz, vp], ctypes.c_int),
+        "coa_certificate_verdict_workspace_bytes": ([sz, sz], sz),
+        "coa_certificate_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp,
+                                                 vp], ctypes.c_int),
+        "coa_message_verdict_workspace_bytes": ([sz], sz),
+        "coa_header_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp], ctypes.c_int),
+        "coa_vote_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp], ctypes.c_int),
+        "coa_cpu_certificate_verdict_many": ([P8, P64, P8, P8, P8, P64, P8, P8, P64, sz, ctypes.c_uint64, vp,
+                                              P8, vp, vp, P64, sz, vp, ctypes.c_int], ctypes.c_int),
+        "coa_cpu_certificate_verdict_from_status": ([P8, P64, P8, P8, P64, P8, P64, sz, vp, P8,
+                                                     P8, vp, vp, P64, sz, vp, ctypes.c_int], ctypes.c_int),
+        "coa_cpu_header_verdict_many": ([P8, P64, P8, P8, P8, sz, vp, P8, vp, vp, P64, sz, vp, ctypes.c_int],
+                                        ctypes.c_int),
+        "coa_cpu_vote_verdict_many": ([P8, P64, P8, P8, P8, sz, P8, vp, vp, P64, sz, vp, ctypes.c_int], ctypes.c_int),
         "coa_queue_create": ([sz, ctypes.c_uint32], vp),
         "coa_queue_submit_verify": ([vp, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
         "coa_queue_submit_verify_many": ([vp, P8, P8, P8, sz, VERDICT_CB, vp], ctypes.c_int),
@@ -777,6 +796,168 @@ def vote_verify_many_device(device, ids, rounds, origins, authors, sigs, status,
     _check(lib().coa_vote_verify_many_device(device, ids.data_ptr(), rounds.data_ptr(), origins.data_ptr(),
                                              authors.data_ptr(), sigs.data_ptr(), ids.shape[0], status.data_ptr(), ws,
                                              _handle(device, stream)))
+
+
+# ------------------------------------------------ verdicts (COA_DAG_* words)
+DAG_OK, DAG_INVALID_HEADER_ID, DAG_UNKNOWN_AUTHOR, DAG_MALFORMED_HEADER, DAG_INVALID_SIGNATURE = 0, 1, 2, 3, 4
+DAG_AUTHORITY_REUSE, DAG_UNKNOWN_VOTER, DAG_REQUIRES_QUORUM, DAG_INVALID_VOTES, DAG_VOTES_OPEN = 5, 6, 7, 8, 9
+MAX_AUTHORITIES = 1024
+
+
+def _committee_arrays(pks, stakes, workers):
+    """config::Committee as the arrays of coa_committee_register_authorities:
+    keys [n, 32], stakes [n], worker ids concatenated, offsets [n + 1]."""
+    pks = np.ascontiguousarray(np.asarray(pks, dtype=np.uint8).reshape(-1, 32))
+    n = pks.shape[0]
+    stakes = np.ascontiguousarray(stakes, dtype=np.uint32).reshape(-1)
+    if stakes.size != n or len(workers) != n:
+        raise ValueError("one stake and one worker list per authority")
+    woff = np.zeros(n + 1, np.uint64)
+    woff[1:] = np.cumsum([len(w) for w in workers])
+    wids = np.array([x for w in workers for x in w] + [0], np.uint32)
+    return pks, stakes, wids, woff, n
+
+
+def committee_register_authorities(pks, stakes, workers):
+    """Register config::Committee -- keys, stakes and each authority's worker
+    ids -- for the verdict calls; everything committee_register does, too.
+    Returns the number of keys."""
+    pks, stakes, wids, woff, n = _committee_arrays(pks, stakes, workers)
+    return _check(lib().coa_committee_register_authorities(_u8p(pks), _u8p(stakes), _u8p(wids), _u64p(woff), n))
+
+
+def _pcounts(payload_counts, n):
+    pc = np.ascontiguousarray(payload_counts, dtype=np.uint32).reshape(-1)
+    if pc.size != n:
+        raise ValueError("one payload count per header")
+    return pc if n else np.zeros(1, np.uint32)
+
+
+def _cert_arrays(header_inputs, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets):
+    n = len(header_inputs)
+    hdata = np.frombuffer(b"".join(bytes(h) for h in header_inputs) + b"\0", np.uint8)
+    hoff = np.zeros(n + 1, np.uint64)
+    hoff[1:] = np.cumsum([len(h) for h in header_inputs])
+    ids, origins, hsigs, vpks, vsigs = (np.ascontiguousarray(a, dtype=np.uint8) for a in
+                                        (ids, origins, header_sigs, vote_pks, vote_sigs))
+    rounds = np.ascontiguousarray(np.broadcast_to(np.asarray(rounds, np.uint64), (n,)))
+    voff = np.ascontiguousarray(vote_offsets, dtype=np.uint64)
+    return n, hdata, hoff, ids, origins, hsigs, rounds, vpks, vsigs, voff
+
+
+def certificate_verdict_many(header_inputs, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets,
+                             payload_counts, rng_seed=0):
+    """Certificate::verify for n certificates, decided by the engine: uint32
+    [n] of DAG_* words (vote index in bits 8-31 for reuse / unknown voter).
+    Needs committee_register_authorities."""
+    n, hdata, hoff, ids, origins, hsigs, rounds, vpks, vsigs, voff = _cert_arrays(
+        header_inputs, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets)
+    pc = _pcounts(payload_counts, n)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_certificate_verdict_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(origins), _u8p(hsigs),
+                                              _u64p(rounds), _u8p(vpks), _u8p(vsigs), _u64p(voff), n, rng_seed,
+                                              _u8p(pc), _u8p(out)))
+    return out[:n]
+
+
+def header_verdict_many(header_inputs, ids, authors, sigs, payload_counts):
+    """Header::verify for n headers: uint32 [n] of DAG_* words."""
+    n, hdata, hoff, ids, authors, sigs = _header_arrays(header_inputs, ids, authors, sigs)
+    pc = _pcounts(payload_counts, n)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_header_verdict_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(authors), _u8p(sigs), n, _u8p(pc),
+                                         _u8p(out)))
+    return out[:n]
+
+
+def vote_verdict_many(ids, rounds, origins, authors, sigs):
+    """Vote::verify for n votes: uint32 [n] of DAG_* words."""
+    n, ids, rounds, origins, authors, sigs = _vote_arrays(ids, rounds, origins, authors, sigs)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_vote_verdict_many(_u8p(ids), _u64p(rounds), _u8p(origins), _u8p(authors), _u8p(sigs), n,
+                                       _u8p(out)))
+    return out[:n]
+
+
+def cpu_certificate_verdict_many(header_inputs, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets,
+                                 payload_counts, committee, rng_seed=0, nthreads=0, status=None):
+    """CPU path of certificate_verdict_many (explicit only; no coa_init
+    needed).  committee = (pks, stakes, workers).  status: the COA_CERT_* bits
+    when the caller holds them already (the protocol checks and merge alone)."""
+    n, hdata, hoff, ids, origins, hsigs, rounds, vpks, vsigs, voff = _cert_arrays(
+        header_inputs, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets)
+    pc = _pcounts(payload_counts, n)
+    cp, cs, cw, co, cn = _committee_arrays(*committee)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    if status is None:
+        _check(lib().coa_cpu_certificate_verdict_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(origins), _u8p(hsigs),
+                                                      _u64p(rounds), _u8p(vpks), _u8p(vsigs), _u64p(voff), n,
+                                                      rng_seed, _u8p(pc), _u8p(cp), _u8p(cs), _u8p(cw), _u64p(co), cn,
+                                                      _u8p(out), nthreads))
+    else:
+        st = np.ascontiguousarray(status, dtype=np.uint8)
+        _check(lib().coa_cpu_certificate_verdict_from_status(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(origins),
+                                                             _u64p(rounds), _u8p(vpks), _u64p(voff), n, _u8p(pc),
+                                                             _u8p(st), _u8p(cp), _u8p(cs), _u8p(cw), _u64p(co), cn,
+                                                             _u8p(out), nthreads))
+    return out[:n]
+
+
+def cpu_header_verdict_many(header_inputs, ids, authors, sigs, payload_counts, committee, nthreads=0):
+    """CPU path of header_verdict_many."""
+    n, hdata, hoff, ids, authors, sigs = _header_arrays(header_inputs, ids, authors, sigs)
+    pc = _pcounts(payload_counts, n)
+    cp, cs, cw, co, cn = _committee_arrays(*committee)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_cpu_header_verdict_many(_u8p(hdata), _u64p(hoff), _u8p(ids), _u8p(authors), _u8p(sigs), n,
+                                             _u8p(pc), _u8p(cp), _u8p(cs), _u8p(cw), _u64p(co), cn, _u8p(out),
+                                             nthreads))
+    return out[:n]
+
+
+def cpu_vote_verdict_many(ids, rounds, origins, authors, sigs, committee, nthreads=0):
+    """CPU path of vote_verdict_many."""
+    n, ids, rounds, origins, authors, sigs = _vote_arrays(ids, rounds, origins, authors, sigs)
+    cp, cs, cw, co, cn = _committee_arrays(*committee)
+    out = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_cpu_vote_verdict_many(_u8p(ids), _u64p(rounds), _u8p(origins), _u8p(authors), _u8p(sigs), n,
+                                           _u8p(cp), _u8p(cs), _u8p(cw), _u64p(co), cn, _u8p(out), nthreads))
+    return out[:n]
+
+
+def certificate_verdict_workspace_bytes(n, n_votes):
+    return lib().coa_certificate_verdict_workspace_bytes(n, n_votes)
+
+
+def message_verdict_workspace_bytes(n):
+    return lib().coa_message_verdict_workspace_bytes(n)
+
+
+def certificate_verdict_many_device(device, hdata, hoff, ids, origins, hsigs, rounds, vpks, vsigs, voff, pcounts,
+                                    verdicts, stream=None, workspace=None):
+    """Device-resident certificates (torch tensors): DAG_* words (uint32
+    tensor [n], may hold DAG_VOTES_OPEN) enqueued on `stream`."""
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_certificate_verdict_many_device(device, hdata.data_ptr(), hoff.data_ptr(), ids.data_ptr(),
+                                                     origins.data_ptr(), hsigs.data_ptr(), rounds.data_ptr(),
+                                                     vpks.data_ptr(), vsigs.data_ptr(), voff.data_ptr(), ids.shape[0],
+                                                     vpks.shape[0], pcounts.data_ptr(), verdicts.data_ptr(), ws,
+                                                     _handle(device, stream)))
+
+
+def header_verdict_many_device(device, hdata, hoff, ids, authors, sigs, pcounts, verdicts, stream=None,
+                               workspace=None):
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_header_verdict_many_device(device, hdata.data_ptr(), hoff.data_ptr(), ids.data_ptr(),
+                                                authors.data_ptr(), sigs.data_ptr(), ids.shape[0], pcounts.data_ptr(),
+                                                verdicts.data_ptr(), ws, _handle(device, stream)))
+
+
+def vote_verdict_many_device(device, ids, rounds, origins, authors, sigs, verdicts, stream=None, workspace=None):
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_vote_verdict_many_device(device, ids.data_ptr(), rounds.data_ptr(), origins.data_ptr(),
+                                              authors.data_ptr(), sigs.data_ptr(), ids.shape[0], verdicts.data_ptr(),
+                                              ws, _handle(device, stream)))
 
 
 class _MsgLatIn(ctypes.Structure):

@@ -42,6 +42,7 @@
 #include <thread>
 #include <vector>
 
+#include "coa_protocol.h"
 #include "coa_verify.h"
 
 namespace {
@@ -833,6 +834,96 @@ int coa_cpu_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const u
       verdicts_out[i] = (uint8_t)verify_strict_one(h, 32, authors + 32 * i, sigs + 64 * i);
     }
   });
+  return COA_OK;
+}
+
+// ------------------------------------------------------------- verdicts
+// The COA_DAG_* words of include/coa_verify.h: the status bits of the calls
+// above merged with the protocol checks of coa_protocol.h, which the GPU
+// path's kernels restate (coa_protocol.hip).
+int coa_cpu_certificate_verdict_from_status(const uint8_t* header_data, const uint64_t* header_offsets,
+                                            const uint8_t* ids, const uint8_t* origins, const uint64_t* rounds,
+                                            const uint8_t* vote_pks, const uint64_t* vote_offsets, size_t n,
+                                            const uint32_t* payload_counts, const uint8_t* status,
+                                            const uint8_t* committee_pks, const uint32_t* stakes,
+                                            const uint32_t* worker_ids, const uint64_t* worker_offsets,
+                                            size_t n_authorities, uint32_t* verdicts_out, int nthreads) {
+  CoaProtTable t;
+  std::string err;
+  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (n == 0) return COA_OK;
+  if (!header_offsets || !ids || !origins || !rounds || !vote_offsets || !payload_counts || !status || !verdicts_out ||
+      vote_offsets[0] != 0)
+    return COA_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (header_offsets[i + 1] < header_offsets[i] || vote_offsets[i + 1] < vote_offsets[i]) return COA_EINVAL;
+  if (header_offsets[n] > header_offsets[0] && !header_data) return COA_EINVAL;
+  if (vote_offsets[n] && !vote_pks) return COA_EINVAL;
+  if (!coa_prot_counts_fit(header_offsets, payload_counts, n)) return COA_EINVAL;
+  parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
+    std::vector<uint32_t> first;
+    for (size_t i = lo; i < hi; i++) {
+      const uint64_t v0 = vote_offsets[i];
+      const uint32_t p = coa_prot_cert_word(t, ids + 32 * i, rounds[i], origins + 32 * i, header_data + header_offsets[i],
+                                            payload_counts[i], vote_pks + 32 * v0, (size_t)(vote_offsets[i + 1] - v0),
+                                            first);
+      verdicts_out[i] = coa_verdict_merge(status[i], p);
+    }
+  });
+  return COA_OK;
+}
+
+int coa_cpu_certificate_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                     const uint8_t* origins, const uint8_t* header_sigs, const uint64_t* rounds,
+                                     const uint8_t* vote_pks, const uint8_t* vote_sigs, const uint64_t* vote_offsets,
+                                     size_t n, uint64_t rng_seed, const uint32_t* payload_counts,
+                                     const uint8_t* committee_pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                     const uint64_t* worker_offsets, size_t n_authorities, uint32_t* verdicts_out,
+                                     int nthreads) {
+  std::vector<uint8_t> st(n + 1, 0);
+  const int rc = coa_cpu_certificate_verify_many(header_data, header_offsets, ids, origins, header_sigs, rounds,
+                                                 vote_pks, vote_sigs, vote_offsets, n, rng_seed, st.data(), nthreads);
+  if (rc != COA_OK) return rc;
+  return coa_cpu_certificate_verdict_from_status(header_data, header_offsets, ids, origins, rounds, vote_pks,
+                                                 vote_offsets, n, payload_counts, st.data(), committee_pks, stakes,
+                                                 worker_ids, worker_offsets, n_authorities, verdicts_out, nthreads);
+}
+
+int coa_cpu_header_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                const uint8_t* authors, const uint8_t* sigs, size_t n, const uint32_t* payload_counts,
+                                const uint8_t* committee_pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                const uint64_t* worker_offsets, size_t n_authorities, uint32_t* verdicts_out,
+                                int nthreads) {
+  CoaProtTable t;
+  std::string err;
+  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (n == 0) return COA_OK;
+  if (!payload_counts || !verdicts_out) return COA_EINVAL;
+  std::vector<uint8_t> st(n, 0);
+  const int rc = coa_cpu_header_verify_many(header_data, header_offsets, ids, authors, sigs, n, st.data(), nthreads);
+  if (rc != COA_OK) return rc;
+  if (!coa_prot_counts_fit(header_offsets, payload_counts, n)) return COA_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    verdicts_out[i] = coa_verdict_merge(
+        st[i], coa_prot_header_word(t, t.slot(authors + 32 * i), header_data + header_offsets[i], payload_counts[i]));
+  return COA_OK;
+}
+
+int coa_cpu_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins,
+                              const uint8_t* authors, const uint8_t* sigs, size_t n, const uint8_t* committee_pks,
+                              const uint32_t* stakes, const uint32_t* worker_ids, const uint64_t* worker_offsets,
+                              size_t n_authorities, uint32_t* verdicts_out, int nthreads) {
+  CoaProtTable t;
+  std::string err;
+  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (n == 0) return COA_OK;
+  if (!verdicts_out) return COA_EINVAL;
+  std::vector<uint8_t> st(n, 0);
+  const int rc = coa_cpu_vote_verify_many(ids, rounds, origins, authors, sigs, n, st.data(), nthreads);
+  if (rc != COA_OK) return rc;
+  for (size_t i = 0; i < n; i++)
+    verdicts_out[i] = coa_verdict_merge(st[i] ? COA_PST_BAD_SIG : 0u, coa_prot_header_word(t, t.slot(authors + 32 * i),
+                                                                                           nullptr, 0));
   return COA_OK;
 }
 

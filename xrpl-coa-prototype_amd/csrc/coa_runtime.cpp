@@ -42,6 +42,8 @@
 #include "coa_halved.h"
 #include "coa_kernels.h"
 #include "coa_latency.h"
+#include "coa_protocol.h"
+#include "coa_protocol_dev.h"
 
 namespace {
 
@@ -171,12 +173,17 @@ struct KeySet {
   uint32_t nkeys = 0;
   bool kwide = false;  // kwtabs holds the committee's wide combs
   bool kw20 = false;   // ... in the radix-2^20 layout (COA_KWCOMB20_*)
+  // protocol table (coa_committee_register_authorities): stake [nkeys] |
+  // worker offsets [nkeys + 1] | worker ids, in the sorted key order
+  DevBuf prot;
+  bool has_prot = false;
+  uint32_t quorum = 0;
   KeySet() = default;
   KeySet(const KeySet&) = delete;
   KeySet& operator=(const KeySet&) = delete;
   ~KeySet() {
     if (dev >= 0) (void)hipSetDevice(dev);
-    for (DevBuf* b : {&ckeys, &kflags, &ktabs, &kwtabs}) b->release();
+    for (DevBuf* b : {&ckeys, &kflags, &ktabs, &kwtabs, &prot}) b->release();
   }
 };
 using KeySetP = std::shared_ptr<const KeySet>;
@@ -351,6 +358,7 @@ struct Dev {
   uint32_t* comb = nullptr;  // 32 x 128 x (v+1)256^j B comb for k_verify_halved (384 KiB)
   DevBuf msgs, pks, sigs, kbuf, rec, verdicts, scratch, aux, rbuf, seeds, offs, data, out, idx, zs, terms, flags;
   DevBuf cert, cscr;
+  DevBuf vws;  // engine-owned workspace of the device-resident verdict calls (under mu)
   DevBuf certc[4], cscrc[4];  // pipelined certificate path: up to four chunks in flight
   PinBuf pinc[4];
   DevBuf msm;  // Pippenger workspace (one large verify_batch group)
@@ -364,7 +372,7 @@ struct Dev {
   std::vector<DevBuf*> all() {
     return {&msgs, &pks,  &sigs,  &kbuf, &rec, &verdicts, &scratch,  &aux,     &rbuf,     &seeds,   &offs, &data,
             &out,  &idx,  &zs,    &terms, &flags, &cert,   &cscr,   &certc[0], &certc[1], &certc[2], &certc[3],
-            &cscrc[0], &cscrc[1], &cscrc[2], &cscrc[3], &msm, &lat};
+            &cscrc[0], &cscrc[1], &cscrc[2], &cscrc[3], &msm, &lat, &vws};
   }
 };
 
@@ -1880,6 +1888,198 @@ int messages_device(int device, MsgArgs a, void* workspace, void* stream) {
   return COA_OK;
 }
 
+// ------------------------------------------------------------------------
+// Verdicts: the crypto status words above merged on the device with the
+// protocol checks of coa_protocol.hip (include/coa_verify.h, COA_DAG_*).
+
+// This thread's launches read generation `ks` for the scope's lifetime, so
+// the crypto launch and the protocol launch of one verdict call see the same
+// committee (a pin the aggregation queue set stays as it is).
+struct KeyScope {
+  const KeySetP* prev;
+  explicit KeyScope(const KeySetP& ks) : prev(t_keys_pinned) {
+    if (!(prev && *prev)) t_keys_pinned = &ks;
+  }
+  ~KeyScope() { t_keys_pinned = prev; }
+};
+
+int prot_tab(const KeySet& ks, ProtTab& t) {
+  if (!ks.has_prot) return fail(COA_EINVAL, "committee registered without stakes");
+  const uint32_t* w = ks.prot.as<uint32_t>();
+  t.keys = ks.ckeys.as<uint32_t>();
+  t.stake = w;
+  t.woff = w + ks.nkeys;
+  t.wids = w + 2 * (size_t)ks.nkeys + 1;
+  t.nk = ks.nkeys;
+  t.quorum = ks.quorum;
+  return COA_OK;
+}
+
+// Certificates [lo, hi) on one context (its lock held): the raw status words
+// of the crypto path, then the protocol kernel and the merge over the arrays
+// those read (one more H2D: no signatures), verdict words out.
+int verdict_cert_shard(Dev& d, const CertIn& in, const uint32_t* pcounts, size_t lo, size_t hi, uint32_t* raw,
+                       uint32_t* out) {
+  const KeySetP ks = keys_now(d);
+  ProtTab t;
+  int rc = prot_tab(*ks, t);
+  if (rc != COA_OK) return rc;
+  const KeyScope scope(ks);
+  rc = cert_shard(d, in, lo, hi, raw);
+  if (rc != COA_OK) return rc;
+  const size_t nc = hi - lo;
+  const uint64_t h0 = in.hdr_off[lo], hb = in.hdr_off[hi] - h0;
+  const uint64_t v0 = in.voff[lo], nv = in.voff[hi] - v0;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes, 256);
+    return at;
+  };
+  const size_t p_verd = take(nc * 4), p_raw = take(nc * 4), p_proto = take(nc * 4), p_pc = take(nc * 4),
+               p_hoff = take((nc + 1) * 8), p_voff = take((nc + 1) * 8), p_rounds = take(nc * 8),
+               p_ids = take(nc * 32), p_origins = take(nc * 32), p_vpks = take(nv * 32), p_hdata = take(hb + 16);
+  HIP_TRY(d.pin.ensure(o));
+  HIP_TRY(d.cert.ensure(o));
+  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
+  uint64_t* ho = reinterpret_cast<uint64_t*>(h + p_hoff);
+  uint64_t* vo = reinterpret_cast<uint64_t*>(h + p_voff);
+  for (size_t i = 0; i <= nc; i++) {
+    ho[i] = in.hdr_off[lo + i] - h0;
+    vo[i] = in.voff[lo + i] - v0;
+  }
+  std::vector<CopyPool::Seg> segs = {{h + p_raw, raw + lo, nc * 4},
+                                     {h + p_pc, pcounts + lo, nc * 4},
+                                     {h + p_rounds, in.rounds + lo, nc * 8},
+                                     {h + p_ids, in.ids + lo * 32, nc * 32},
+                                     {h + p_origins, in.origins + lo * 32, nc * 32}};
+  if (nv) segs.push_back({h + p_vpks, in.vpks + v0 * 32, nv * 32});
+  if (hb) segs.push_back({h + p_hdata, in.hdr_data + h0, hb});
+  CopyPool::get().copy(segs);
+  hipStream_t s = d.stream;
+  uint8_t* base = d.cert.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(base + p_raw, h + p_raw, o - p_raw, hipMemcpyHostToDevice, s));
+  CertProtArgs a{};
+  a.hdr_data = base + p_hdata;
+  a.hdr_off = reinterpret_cast<const uint64_t*>(base + p_hoff);
+  a.ids = reinterpret_cast<const uint32_t*>(base + p_ids);
+  a.origins = reinterpret_cast<const uint32_t*>(base + p_origins);
+  a.rounds = reinterpret_cast<const uint64_t*>(base + p_rounds);
+  a.vpks = reinterpret_cast<const uint32_t*>(base + p_vpks);
+  a.voff = reinterpret_cast<const uint64_t*>(base + p_voff);
+  a.pcounts = reinterpret_cast<const uint32_t*>(base + p_pc);
+  a.nc = (uint32_t)nc;
+  a.nv = (uint32_t)nv;
+  a.proto = reinterpret_cast<uint32_t*>(base + p_proto);
+  HIP_TRY(coa_launch_cert_protocol(a, t, s));
+  HIP_TRY(coa_launch_verdict_merge(reinterpret_cast<const uint32_t*>(base + p_raw), a.proto,
+                                   reinterpret_cast<uint32_t*>(base + p_verd), (uint32_t)nc, s));
+  HIP_TRY(hipMemcpyAsync(h + p_verd, base + p_verd, nc * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(out + lo, h + p_verd, nc * 4);
+  return COA_OK;
+}
+
+// The same for headers and votes.
+int verdict_msg_shard(Dev& d, const MsgIn& in, const uint32_t* pcounts, size_t lo, size_t hi, uint32_t* raw,
+                      uint32_t* out) {
+  const KeySetP ks = keys_now(d);
+  ProtTab t;
+  int rc = prot_tab(*ks, t);
+  if (rc != COA_OK) return rc;
+  const KeyScope scope(ks);
+  rc = msg_shard(d, in, lo, hi, raw);
+  if (rc != COA_OK) return rc;
+  const size_t n = hi - lo;
+  const uint64_t h0 = in.votes ? 0 : in.hdr_off[lo], hb = in.votes ? 0 : in.hdr_off[hi] - h0;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o = align_up(o + bytes, 256);
+    return at;
+  };
+  const size_t p_verd = take(n * 4), p_raw = take(n * 4), p_proto = take(n * 4), p_authors = take(n * 32),
+               p_pc = take(in.votes ? 0 : n * 4), p_hoff = take(in.votes ? 0 : (n + 1) * 8),
+               p_hdata = take(in.votes ? 0 : hb + 16);
+  HIP_TRY(d.pin.ensure(o));
+  HIP_TRY(d.cert.ensure(o));
+  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
+  std::vector<CopyPool::Seg> segs = {{h + p_raw, raw + lo, n * 4}, {h + p_authors, in.authors + lo * 32, n * 32}};
+  if (!in.votes) {
+    uint64_t* ho = reinterpret_cast<uint64_t*>(h + p_hoff);
+    for (size_t i = 0; i <= n; i++) ho[i] = in.hdr_off[lo + i] - h0;
+    segs.push_back({h + p_pc, pcounts + lo, n * 4});
+    if (hb) segs.push_back({h + p_hdata, in.hdr_data + h0, hb});
+  }
+  CopyPool::get().copy(segs);
+  hipStream_t s = d.stream;
+  uint8_t* base = d.cert.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(base + p_raw, h + p_raw, o - p_raw, hipMemcpyHostToDevice, s));
+  MsgProtArgs a{};
+  if (!in.votes) {
+    a.hdr_data = base + p_hdata;
+    a.hdr_off = reinterpret_cast<const uint64_t*>(base + p_hoff);
+    a.pcounts = reinterpret_cast<const uint32_t*>(base + p_pc);
+  }
+  a.authors = reinterpret_cast<const uint32_t*>(base + p_authors);
+  a.n = (uint32_t)n;
+  a.proto = reinterpret_cast<uint32_t*>(base + p_proto);
+  HIP_TRY(coa_launch_msg_protocol(a, t, s));
+  HIP_TRY(coa_launch_verdict_merge(reinterpret_cast<const uint32_t*>(base + p_raw), a.proto,
+                                   reinterpret_cast<uint32_t*>(base + p_verd), (uint32_t)n, s));
+  HIP_TRY(hipMemcpyAsync(h + p_verd, base + p_verd, n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(out + lo, h + p_verd, n * 4);
+  return COA_OK;
+}
+
+int message_verdicts(const MsgIn& in, const uint32_t* pcounts, size_t n, uint32_t* out) {
+  std::vector<uint32_t> raw(n, 0);
+  return for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int {
+    return verdict_msg_shard(d, in, pcounts, lo, hi, raw.data(), out);
+  });
+}
+
+// Device-resident verdict calls: `crypto` enqueues the *_verify_many_device
+// launch with its raw words at `raw` and its workspace at `ws`; the protocol
+// kernel and the merge follow on the same stream.  workspace NULL: the
+// context's own, and the call waits for its stream.
+size_t verdict_ws_bytes(size_t crypto_bytes, size_t n) { return align_up(crypto_bytes, 256) + 2 * align_up(n * 4, 256); }
+
+template <class Crypto, class Proto>
+int verdicts_device(int device, size_t n, size_t crypto_bytes, uint32_t* d_verdicts, void* workspace, void* stream,
+                    Crypto crypto, Proto proto) {
+  Dev* d = dev_by_id(device);
+  if (!d) return fail(COA_EINVAL, "device not opened by coa_init");
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t s = stream ? (hipStream_t)stream : d->stream;
+  const KeySetP ks = keys_now(*d);
+  ProtTab t;
+  int rc = prot_tab(*ks, t);
+  if (rc != COA_OK) return rc;
+  std::unique_lock<std::mutex> own;
+  if (!workspace) {
+    own = std::unique_lock<std::mutex>(d->mu);  // the crypto call below gets a workspace: it takes no lock
+    HIP_TRY(d->vws.ensure(verdict_ws_bytes(crypto_bytes, n)));
+    workspace = d->vws.p;
+  }
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* raw = reinterpret_cast<uint32_t*>(ws + align_up(crypto_bytes, 256));
+  uint32_t* pw = reinterpret_cast<uint32_t*>(ws + align_up(crypto_bytes, 256) + align_up(n * 4, 256));
+  {
+    const KeyScope scope(ks);
+    rc = crypto(raw, ws, s);
+    if (rc != COA_OK) return rc;
+  }
+  HIP_TRY(proto(pw, t, s));
+  HIP_TRY(coa_launch_verdict_merge(raw, pw, d_verdicts, (uint32_t)n, s));
+  if (own.owns_lock()) {
+    HIP_TRY(hipStreamSynchronize(s));  // engine-owned workspace: drain before release
+    return COA_OK;
+  }
+  return trail_keys(*d, ks, s);
+}
+
 int sign_enqueue(Dev& d, const uint8_t* d_seeds, const uint8_t* d_msgs, size_t msg_len, size_t n, uint8_t* d_pks,
                  uint8_t* d_sigs, hipStream_t s) {
   HIP_TRY(d.aux.ensure(n * 64 + 64));
@@ -1900,7 +2100,7 @@ int sign_enqueue(Dev& d, const uint8_t* d_seeds, const uint8_t* d_msgs, size_t m
 // frees the old generation once nothing holds it: no call or window waits
 // for a registration, and none is held back (the round-3 write gate stalled
 // the queue's certificate windows for the whole 0.6-2.7 s build).
-int build_keyset(DevShared& sh, const std::vector<std::array<uint32_t, 8>>& keys) {
+int build_keyset(DevShared& sh, const std::vector<std::array<uint32_t, 8>>& keys, const CoaProtTable* pt = nullptr) {
   std::lock_guard<std::mutex> r(sh.reg_mu);
   HIP_TRY(hipSetDevice(sh.id));
   if (!sh.build) {
@@ -1945,6 +2145,7 @@ int build_keyset(DevShared& sh, const std::vector<std::array<uint32_t, 8>>& keys
   ks->dev = sh.id;
   ks->nkeys = 0;
   ks->kwide = ks->kw20 = false;
+  ks->has_prot = false;
   hipStream_t s = sh.build;
   // COA_REGISTER_TRACE=1: phase times of this registration on stderr
   using clk = std::chrono::steady_clock;
@@ -2004,6 +2205,16 @@ int build_keyset(DevShared& sh, const std::vector<std::array<uint32_t, 8>>& keys
     HIP_TRY(hipStreamSynchronize(s));
     k.nkeys = (uint32_t)nk;
     t_built = clk::now();
+  }
+  if (pt) {  // the protocol table of this generation, in the same key order
+    std::vector<uint32_t> w(pt->stake);
+    w.insert(w.end(), pt->woff.begin(), pt->woff.end());
+    w.insert(w.end(), pt->wids.begin(), pt->wids.end());
+    HIP_TRY(ks->prot.ensure(w.size() * 4));
+    HIP_TRY(hipMemcpyAsync(ks->prot.p, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    ks->quorum = pt->quorum;
+    ks->has_prot = true;
   }
   KeySetP old;
   {
@@ -2893,6 +3104,192 @@ int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t
   a.n = (uint32_t)n;
   a.status = d_status;
   return messages_device(device, a, workspace, stream);
+}
+
+// ------------------------------------------------------------- verdicts
+int coa_committee_register_authorities(const uint8_t* pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                                       const uint64_t* worker_offsets, size_t n) {
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  CoaProtTable pt;
+  std::string err;
+  if (!coa_prot_build(pks, stakes, worker_ids, worker_offsets, n, pt, err)) return fail(COA_EINVAL, err);
+  std::vector<std::pair<Dev*, std::function<int()>>> tasks;
+  for (auto& shp : g_shared) {
+    DevShared* sh = shp.get();
+    Dev* first = nullptr;
+    for (auto& dp : g_devs)
+      if (dp->id == sh->id && !first) first = dp.get();
+    if (!first) continue;
+    tasks.emplace_back(first, [sh, &pt]() -> int { return build_keyset(*sh, pt.keys, &pt); });
+  }
+  rc = run_tasks(tasks);
+  if (rc != COA_OK) return rc;
+  return (int)pt.keys.size();
+}
+
+int coa_certificate_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                                 const uint8_t* origins, const uint8_t* header_sigs, const uint64_t* rounds,
+                                 const uint8_t* vote_pks, const uint8_t* vote_sigs, const uint64_t* vote_offsets,
+                                 size_t n, uint64_t rng_seed, const uint32_t* payload_counts,
+                                 uint32_t* verdicts_out) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  const CertIn in{header_data, header_offsets, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets};
+  if (!in.hdr_off || !in.ids || !in.origins || !in.hsigs || !in.rounds || !in.voff || !payload_counts || !verdicts_out)
+    return fail(COA_EINVAL, "null argument");
+  for (size_t i = 0; i < n; i++)
+    if (in.hdr_off[i + 1] < in.hdr_off[i] || in.voff[i + 1] < in.voff[i])
+      return fail(COA_EINVAL, "offsets not monotone");
+  if (in.voff[0] != 0) return fail(COA_EINVAL, "vote_offsets[0] must be 0");
+  if (in.hdr_off[n] > in.hdr_off[0] && !in.hdr_data) return fail(COA_EINVAL, "null header data");
+  if (in.voff[n] && (!in.vpks || !in.vsigs)) return fail(COA_EINVAL, "null vote arrays");
+  if (check_n(n + in.voff[n]) != COA_OK) return COA_EINVAL;
+  if (!coa_prot_counts_fit(in.hdr_off, payload_counts, n))
+    return fail(COA_EINVAL, "a payload count overruns its header");
+  std::vector<uint32_t> raw(n, 0);
+  rc = for_shards(
+      n,
+      [&](Dev& d, size_t lo, size_t hi) -> int {
+        return verdict_cert_shard(d, in, payload_counts, lo, hi, raw.data(), verdicts_out);
+      },
+      n + in.voff[n]);
+  if (rc != COA_OK) return rc;
+  // what stays open: every earlier check passed and the votes need the exact
+  // random-linear-combination check
+  std::vector<size_t> open;
+  for (size_t i = 0; i < n; i++)
+    if (verdicts_out[i] == COA_DAG_VOTES_OPEN) open.push_back(i);
+  if (open.empty()) return COA_OK;
+  std::vector<uint32_t> st(n, 0);
+  rc = cert_resolve(in, open, false, rng_seed ? rng_seed : os_entropy_seed(), st.data());
+  if (rc != COA_OK) return rc;
+  for (size_t i : open) verdicts_out[i] = (st[i] & COA_CST_BAD_VOTES) ? COA_DAG_INVALID_VOTES : COA_DAG_OK;
+  return COA_OK;
+}
+
+int coa_header_verdict_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
+                            const uint8_t* authors, const uint8_t* sigs, size_t n, const uint32_t* payload_counts,
+                            uint32_t* verdicts_out) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!header_offsets || !ids || !authors || !sigs || !payload_counts || !verdicts_out)
+    return fail(COA_EINVAL, "null argument");
+  for (size_t i = 0; i < n; i++)
+    if (header_offsets[i + 1] < header_offsets[i]) return fail(COA_EINVAL, "offsets not monotone");
+  if (header_offsets[n] > header_offsets[0] && !header_data) return fail(COA_EINVAL, "null header data");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  if (!coa_prot_counts_fit(header_offsets, payload_counts, n))
+    return fail(COA_EINVAL, "a payload count overruns its header");
+  const MsgIn in{header_data, header_offsets, ids, nullptr, nullptr, authors, sigs, false};
+  return message_verdicts(in, payload_counts, n, verdicts_out);
+}
+
+int coa_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
+                          const uint8_t* sigs, size_t n, uint32_t* verdicts_out) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!ids || !rounds || !origins || !authors || !sigs || !verdicts_out) return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  const MsgIn in{nullptr, nullptr, ids, rounds, origins, authors, sigs, true};
+  return message_verdicts(in, nullptr, n, verdicts_out);
+}
+
+size_t coa_certificate_verdict_workspace_bytes(size_t n, size_t n_votes) {
+  return verdict_ws_bytes(coa_certificate_workspace_bytes(n, n_votes), n);
+}
+
+int coa_certificate_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                        const uint8_t* d_ids, const uint8_t* d_origins, const uint8_t* d_header_sigs,
+                                        const uint64_t* d_rounds, const uint8_t* d_vote_pks,
+                                        const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
+                                        size_t n_votes, const uint32_t* d_payload_counts, uint32_t* d_verdicts,
+                                        void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!d_header_offsets || !d_ids || !d_origins || !d_header_sigs || !d_rounds || !d_vote_offsets ||
+      !d_payload_counts || !d_verdicts || (n_votes && (!d_vote_pks || !d_vote_sigs)))
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n + n_votes) != COA_OK) return COA_EINVAL;
+  return verdicts_device(
+      device, n, coa_certificate_workspace_bytes(n, n_votes), d_verdicts, workspace, stream,
+      [&](uint32_t* raw, void* ws, hipStream_t s) {
+        return coa_certificate_verify_many_device(device, d_header_data, d_header_offsets, d_ids, d_origins,
+                                                  d_header_sigs, d_rounds, d_vote_pks, d_vote_sigs, d_vote_offsets, n,
+                                                  n_votes, raw, ws, s);
+      },
+      [&](uint32_t* pw, const ProtTab& t, hipStream_t s) {
+        CertProtArgs a{};
+        a.hdr_data = d_header_data;
+        a.hdr_off = d_header_offsets;
+        a.ids = reinterpret_cast<const uint32_t*>(d_ids);
+        a.origins = reinterpret_cast<const uint32_t*>(d_origins);
+        a.rounds = d_rounds;
+        a.vpks = reinterpret_cast<const uint32_t*>(d_vote_pks);
+        a.voff = d_vote_offsets;
+        a.pcounts = d_payload_counts;
+        a.nc = (uint32_t)n;
+        a.nv = (uint32_t)n_votes;
+        a.proto = pw;
+        return coa_launch_cert_protocol(a, t, s);
+      });
+}
+
+size_t coa_message_verdict_workspace_bytes(size_t n) { return verdict_ws_bytes(coa_message_workspace_bytes(n), n); }
+
+int coa_header_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
+                                   const uint8_t* d_ids, const uint8_t* d_authors, const uint8_t* d_sigs, size_t n,
+                                   const uint32_t* d_payload_counts, uint32_t* d_verdicts, void* workspace,
+                                   void* stream) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!d_header_data || !d_header_offsets || !d_ids || !d_authors || !d_sigs || !d_payload_counts || !d_verdicts)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  return verdicts_device(
+      device, n, coa_message_workspace_bytes(n), d_verdicts, workspace, stream,
+      [&](uint32_t* raw, void* ws, hipStream_t s) {
+        return coa_header_verify_many_device(device, d_header_data, d_header_offsets, d_ids, d_authors, d_sigs, n, raw,
+                                             ws, s);
+      },
+      [&](uint32_t* pw, const ProtTab& t, hipStream_t s) {
+        MsgProtArgs a{};
+        a.hdr_data = d_header_data;
+        a.hdr_off = d_header_offsets;
+        a.pcounts = d_payload_counts;
+        a.authors = reinterpret_cast<const uint32_t*>(d_authors);
+        a.n = (uint32_t)n;
+        a.proto = pw;
+        return coa_launch_msg_protocol(a, t, s);
+      });
+}
+
+int coa_vote_verdict_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
+                                 const uint8_t* d_authors, const uint8_t* d_sigs, size_t n, uint32_t* d_verdicts,
+                                 void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!d_ids || !d_rounds || !d_origins || !d_authors || !d_sigs || !d_verdicts)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK) return COA_EINVAL;
+  return verdicts_device(
+      device, n, coa_message_workspace_bytes(n), d_verdicts, workspace, stream,
+      [&](uint32_t* raw, void* ws, hipStream_t s) {
+        return coa_vote_verify_many_device(device, d_ids, d_rounds, d_origins, d_authors, d_sigs, n, raw, ws, s);
+      },
+      [&](uint32_t* pw, const ProtTab& t, hipStream_t s) {
+        MsgProtArgs a{};
+        a.authors = reinterpret_cast<const uint32_t*>(d_authors);
+        a.n = (uint32_t)n;
+        a.proto = pw;
+        return coa_launch_msg_protocol(a, t, s);
+      });
 }
 
 }  // extern "C"
