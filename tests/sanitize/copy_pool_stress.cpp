@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "coa_stage.h"  // Seg
 #include "copy_pool_class.inc"
 
 int main() {
@@ -27,7 +28,7 @@ int main() {
         const size_t n = (size_t)(1 << 20) * (1 + (it + t) % 5) + 12345;
         std::vector<uint8_t> a(n), b(n, 0);
         for (size_t i = 0; i < n; i += 4093) a[i] = (uint8_t)(i * 7 + t + it);
-        std::vector<CopyPool::Seg> segs;
+        std::vector<Seg> segs;
         for (size_t o = 0; o < n; o += 300000) segs.push_back({b.data() + o, a.data() + o, std::min<size_t>(300000, n - o)});
         CopyPool::get().copy(segs);
         if (a != b) bad++;

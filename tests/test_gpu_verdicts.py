@@ -116,6 +116,56 @@ def test_device_forms_match_and_open_only_where_allowed(registered, own):
     assert not _diff(vt, _words(out), vc.expected_votes())
 
 
+def _tiled_certificates(k):
+    """k tiles of the certificate cases: the call's arguments, its expected
+    words and the oracle's crypto bits (co.certificate_verify_many over one
+    tile, as expected_certificates calls it) with the certificates whose
+    vote bit depends on the weights."""
+    import coa_oracle as co
+
+    h, ids, origins, hsigs, rounds, vp, vs, off, counts = vc.certificate_arrays(vc.certificate_cases())
+    bits = co.certificate_verify_many(h, ids, origins, hsigs, rounds, vp, vs, off,
+                                      np.random.default_rng(3).integers(0, 256, (vp.shape[0], 16), dtype=np.uint8))
+    toff = np.concatenate([[0]] + [off[1:] + t * off[-1] for t in range(k)]).astype(np.uint64)
+    args = (list(h) * k, np.tile(ids, (k, 1)), np.tile(origins, (k, 1)), np.tile(hsigs, (k, 1)), np.tile(rounds, k),
+            np.tile(vp, (k, 1)), np.tile(vs, (k, 1)), toff, list(counts) * k)
+    # verify_batch over a vote by a key with a torsion component answers by
+    # its random weights (test_gpu_committee.py, weight-dependent classes), and
+    # the engine draws its own: that certificate's vote bit has no one answer
+    torsion = {vc.committee().w.mx_pk, vc.committee().w.small_pk, vc.committee().w.off_pk}
+    by_weights = np.array([any(pk in torsion for pk, _ in c["votes"]) for c in vc.certificate_cases()])
+    return (args, np.tile(vc.expected_certificates()[0], k), np.tile(np.asarray(bits, np.uint8), k),
+            np.tile(by_weights, k))
+
+
+def test_verdicts_through_the_pipelined_certificate_path(registered, monkeypatch):
+    """6 tiles of the cases are 432 certificates and 12,342 jobs: with
+    COA_CERT_CHUNK_JOBS=4096 (the least the runtime accepts) the call is at
+    least twice a chunk, so it takes the pipelined path, in at least 4 chunks
+    (the first closes at 2,048 jobs; tests/sanitize/stage_driver.cpp checks
+    the cuts of this very set) over 2 buffer sets: a set is reused, chunks
+    start at lo > 0, and each chunk's protocol tail runs on its own stream.
+    The crypto-only call goes the same way with no tail."""
+    e = registered
+    args, want, bits, by_weights = _tiled_certificates(6)
+    assert len(args[0]) + int(args[7][-1]) == 12_342
+    monkeypatch.setenv("COA_CERT_CHUNK_JOBS", "4096")
+    monkeypatch.setenv("COA_CERT_BUFFERS", "2")
+    piped = e.certificate_verdict_many(*args, rng_seed=7)
+    crypto = e.certificate_verify_many(*args[:8], rng_seed=7)
+    monkeypatch.setenv("COA_CERT_PIPELINE", "0")
+    whole = e.certificate_verdict_many(*args, rng_seed=7)
+    crypto_whole = e.certificate_verify_many(*args[:8], rng_seed=7)
+    names = [{"name": f"{c['name']}#{t}"} for t in range(6) for c in vc.certificate_cases()]
+    assert not _diff(names, piped, want)
+    assert not _diff(names, whole, want)
+    print("vote bit by the weights:", [n["name"] for n, w in zip(names, by_weights) if w][:12])
+    assert by_weights.sum() <= 6 * 4  # a few cases of the 72
+    mask = np.where(by_weights, 3, 7).astype(np.uint8)  # BAD_VOTES is bit 2
+    assert not _diff(names, crypto & mask, bits & mask)
+    assert not _diff(names, crypto, crypto_whole)  # same seed, same weights: every bit
+
+
 def test_device_form_answers_an_overrunning_count_malformed(registered):
     cases = [dict(c) for c in vc.certificate_cases() if c["name"] in ("payload_1", "clean_a")]
     for c in cases:
@@ -192,3 +242,34 @@ def test_reregistration_changes_the_quorum_then_plain_registration_refuses(regis
     finally:
         e.committee_register_authorities(pks, stakes, workers)
     assert list(e.certificate_verdict_many(*args)) == [vc.OK, vc.QUORUM]
+
+
+def test_host_forms_over_two_contexts(registered, monkeypatch):
+    """Two contexts on device 0 and a small COA_MIN_SHARD: every host form
+    runs as two index-range shards, the second with lo > 0 -- for a header
+    shard the only way to a rebased header-offset array.  COA_MIN_SHARD=64
+    gives 186 headers 2 shards and the certificates (2,057 jobs) 2; the 102
+    votes need 32 (102 / 64 is one shard).  Last in the file: it re-opens the
+    engine."""
+    e = registered
+    auth = vc.committee().arrays()
+    try:
+        e.shutdown()
+        e.init_devices([0, 0])
+        e.committee_register_authorities(*auth)
+        monkeypatch.setenv("COA_MIN_SHARD", "64")
+        hc, cc = vc.header_cases(), vc.certificate_cases()
+        assert len(hc) // 64 >= 2 and (len(cc) + sum(len(c["votes"]) for c in cc)) // 64 >= 2
+        got = e.header_verdict_many(*vc.header_arrays(hc))
+        assert not _diff(hc, got, vc.expected_headers())
+        got = e.certificate_verdict_many(*vc.certificate_arrays(cc), rng_seed=7)
+        assert not _diff(cc, got, vc.expected_certificates()[0])
+        monkeypatch.setenv("COA_MIN_SHARD", "32")
+        vt = vc.vote_cases()
+        assert len(vt) // 32 >= 2
+        got = e.vote_verdict_many(*vc.vote_arrays(vt))
+        assert not _diff(vt, got, vc.expected_votes())
+    finally:
+        e.shutdown()
+        e.init(0)
+        e.committee_register_authorities(*auth)

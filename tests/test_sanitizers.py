@@ -114,7 +114,7 @@ def test_copy_pool_concurrent_jobs(san):
     second lookup after the wait raced the other workers' claims and came
     back empty: a null job, SIGSEGV on a GPU box)."""
     inc = _copy_pool_inc(os.path.join(ROOT, "tests", "sanitize", "_build"))
-    flags = ["-fsanitize=" + san, "-fno-sanitize-recover=all", "-I", inc]
+    flags = ["-fsanitize=" + san, "-fno-sanitize-recover=all", "-I", inc, "-I", CSRC]
     cxx = CLANG if san == "thread" and os.path.exists(CLANG) else "g++"
     exe = _build(os.path.join(inc, "copy_pool_" + san.split(",")[0]),
                  [os.path.join(ROOT, "tests", "sanitize", "copy_pool_stress.cpp")], flags, cxx=cxx)

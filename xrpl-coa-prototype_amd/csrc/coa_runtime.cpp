@@ -33,6 +33,7 @@
 #include <random>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -44,6 +45,7 @@
 #include "coa_latency.h"
 #include "coa_protocol.h"
 #include "coa_protocol_dev.h"
+#include "coa_stage.h"
 
 namespace {
 
@@ -225,31 +227,27 @@ struct DevShared {
 // (default 8, at most 16) threads including the caller.
 class CopyPool {
  public:
-  struct Seg {
-    void* dst;
-    const void* src;
-    size_t bytes;
-  };
   static CopyPool& get() {
     static CopyPool pool;
     return pool;
   }
   // Copies every segment, pieces of at most kPiece bytes spread over the pool.
-  void copy(const std::vector<Seg>& segs) {
+  void copy(const std::vector<Seg>& segs) { copy(segs.data(), segs.size()); }
+  void copy(const Seg* segs, size_t n) {
     // Below kInline bytes the caller copies alone: waking the pool
     // (notify_all of 7 threads + a done_cv wait) cost one C3 certificate
     // (~10 KB in 7 segments) ~27 us of its 0.12 ms p50 in round 4.
     size_t total = 0;
-    for (const Seg& g : segs) total += g.bytes;
+    for (const Seg* g = segs; g != segs + n; g++) total += g->bytes;
     if (total < kInline) {
-      for (const Seg& g : segs) std::memcpy(g.dst, g.src, g.bytes);
+      for (const Seg* g = segs; g != segs + n; g++) std::memcpy(g->dst, g->src, g->bytes);
       return;
     }
     std::vector<Seg> pieces;
-    for (const Seg& g : segs)
-      for (size_t o = 0; o < g.bytes; o += kPiece)
-        pieces.push_back({static_cast<uint8_t*>(g.dst) + o, static_cast<const uint8_t*>(g.src) + o,
-                          std::min(kPiece, g.bytes - o)});
+    for (const Seg* g = segs; g != segs + n; g++)
+      for (size_t o = 0; o < g->bytes; o += kPiece)
+        pieces.push_back({static_cast<uint8_t*>(g->dst) + o, static_cast<const uint8_t*>(g->src) + o,
+                          std::min(kPiece, g->bytes - o)});
     // chunks of consecutive pieces of >= kChunk bytes, claimed with one atomic
     // add each: a queue window of C3 certificates is ~2,000 segments of a few
     // KB, and a mutex per segment made eight threads copy at 3 GB/s
@@ -448,6 +446,23 @@ KeySetP keys_now(const Dev& d) {
   return d.sh->keys;
 }
 
+// The key tables of generation ks and context d's fixed-base combs into the
+// arguments of any committee kernel; the wide combs too, except for the
+// latency kernels (LatArgs and MsgLatArgs have no fields for them).
+template <class A>
+void key_args(A& a, const Dev& d, const KeySet& ks) {
+  a.keys = ks.ckeys.as<uint32_t>();
+  a.kflags = ks.kflags.as<uint32_t>();
+  a.ktabs = ks.ktabs.as<uint32_t>();
+  a.nk = ks.nkeys;
+  a.comb = d.comb;
+  if constexpr (!std::is_same_v<A, LatArgs> && !std::is_same_v<A, MsgLatArgs>) {
+    a.wcomb = wcomb_of(d);
+    a.kwtabs = (ks.kwide && !env_is("COA_KEY_WCOMB", "0")) ? ks.kwtabs.as<uint32_t>() : nullptr;
+    a.kw20 = ks.kw20 ? 1u : 0u;
+  }
+}
+
 // Drops the trailing generations whose kernels have completed (an event in
 // error counts as complete: nothing more will read through it).
 void reap_trailing(DevShared& sh) {
@@ -570,8 +585,6 @@ Dev* dev_by_id(int device) {
     if (d->id == device) return d.get();
   return nullptr;
 }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 uint32_t verify_lanes(size_t n) {
   const size_t lanes = align_up(std::max<size_t>(n, 1), COA_VERIFY_BLOCK);
@@ -835,11 +848,7 @@ int lat_verify(Dev& d, const uint8_t* msgs, const uint8_t* pks, const uint8_t* s
   a.tag = tag;
   a.res = d.lat_res;
   const KeySetP ks = keys_now(d);  // held until the verdicts are in
-  a.keys = ks->ckeys.as<uint32_t>();
-  a.kflags = ks->kflags.as<uint32_t>();
-  a.ktabs = ks->ktabs.as<uint32_t>();
-  a.nk = ks->nkeys;
-  a.comb = d.comb;
+  key_args(a, d, *ks);
   HIP_TRY(coa_launch_verify_lat(a, s));
   std::vector<uint32_t> words(n);
   rc = lat_res_wait(d, s, n, tag, words.data());
@@ -1233,20 +1242,8 @@ int batch_groups_impl(const uint8_t* msgs, const uint8_t* pks, const uint8_t* si
 
 // ------------------------------------------------------------------------
 // Certificate::verify crypto (f2 + f3).  Inputs of a shard [lo, hi) are
-// packed into the device's pinned staging buffer and copied with ONE H2D; the
-// status words come back with one D2H.
-struct CertIn {
-  const uint8_t* hdr_data;
-  const uint64_t* hdr_off;
-  const uint8_t* ids;
-  const uint8_t* origins;
-  const uint8_t* hsigs;
-  const uint64_t* rounds;
-  const uint8_t* vpks;
-  const uint8_t* vsigs;
-  const uint64_t* voff;
-};
-
+// packed into the device's pinned staging buffer (coa_stage.h) and copied
+// with ONE H2D; the status words come back with one D2H.
 // COA_CERT_LANES=1|64 forces the lanes-per-signature variant.
 int cert_lanes(size_t jobs) {
   const char* e = getenv("COA_CERT_LANES");
@@ -1255,151 +1252,111 @@ int cert_lanes(size_t jobs) {
   return jobs <= 2048 ? 64 : 1;
 }
 
-struct CertPack {
-  size_t status, hoff, ids, origins, hsigs, rounds, voff, vpks, vsigs, hdata, total;
-};
-CertPack cert_layout(size_t nc, size_t nv, size_t hbytes) {
-  CertPack p;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  p.status = take(nc * 4);
-  p.hoff = take((nc + 1) * 8);
-  p.ids = take(nc * 32);
-  p.origins = take(nc * 32);
-  p.hsigs = take(nc * 64);
-  p.rounds = take(nc * 8);
-  p.voff = take((nc + 1) * 8);
-  p.vpks = take(nv * 32);
-  p.vsigs = take(nv * 64);
-  p.hdata = take(hbytes + 16);
-  p.total = o;
-  return p;
-}
-
-CertArgs cert_args(Dev& d, const KeySet& ks, uint8_t* base, const CertPack& p, size_t nc, size_t nv) {
+// The arrays of a certificate launch, device pointers (status and the key
+// tables are the caller's to set).
+CertArgs cert_args(const uint8_t* hdr_data, const uint64_t* hdr_off, const uint8_t* ids, const uint8_t* origins,
+                   const uint8_t* hsigs, const uint64_t* rounds, const uint8_t* vpks, const uint8_t* vsigs,
+                   const uint64_t* voff, size_t nc, size_t nv) {
   CertArgs a;
-  a.hdr_data = base + p.hdata;
-  a.hdr_off = reinterpret_cast<const uint64_t*>(base + p.hoff);
-  a.ids = reinterpret_cast<const uint32_t*>(base + p.ids);
-  a.origins = reinterpret_cast<const uint32_t*>(base + p.origins);
-  a.hsigs = reinterpret_cast<const uint32_t*>(base + p.hsigs);
-  a.rounds = reinterpret_cast<const uint64_t*>(base + p.rounds);
-  a.vpks = reinterpret_cast<const uint32_t*>(base + p.vpks);
-  a.vsigs = reinterpret_cast<const uint32_t*>(base + p.vsigs);
-  a.voff = reinterpret_cast<const uint64_t*>(base + p.voff);
+  a.hdr_data = hdr_data;
+  a.hdr_off = hdr_off;
+  a.ids = reinterpret_cast<const uint32_t*>(ids);
+  a.origins = reinterpret_cast<const uint32_t*>(origins);
+  a.hsigs = reinterpret_cast<const uint32_t*>(hsigs);
+  a.rounds = rounds;
+  a.vpks = reinterpret_cast<const uint32_t*>(vpks);
+  a.vsigs = reinterpret_cast<const uint32_t*>(vsigs);
+  a.voff = voff;
   a.nc = (uint32_t)nc;
   a.nv = (uint32_t)nv;
   a.hdr_blocks = 0;
-  a.keys = ks.ckeys.as<uint32_t>();
-  a.kflags = ks.kflags.as<uint32_t>();
-  a.ktabs = ks.ktabs.as<uint32_t>();
-  a.nk = ks.nkeys;
-  a.comb = d.comb;
-  a.wcomb = wcomb_of(d);
-  a.kwtabs = (ks.kwide && !env_is("COA_KEY_WCOMB", "0")) ? ks.kwtabs.as<uint32_t>() : nullptr;
-  a.kw20 = ks.kw20 ? 1u : 0u;
-  a.status = reinterpret_cast<uint32_t*>(base + p.status);
   return a;
 }
 
-// Fast path for certificates [lo, hi) on one device: raw status words out.
-// publish: the latency variant writes its status words straight into
-// page-locked host memory (no D2H copy, no stream synchronisation).
-// The latency launch with the certificates inline in the kernel arguments
-// (no pinned staging copy, no H2D transfer): for calls whose arrays fit
-// COA_CERT_INLINE_BYTES.  Returns 1 when they do not fit (nothing launched).
-// Certificates [lo, hi) of `in` into ci's buffer; false when they do not fit.
+// The launch over a block laid out as p at device address base, on
+// generation ks.
+CertArgs cert_args_packed(const Dev& d, const KeySet& ks, uint8_t* base, const CertPack& p, size_t nc, size_t nv) {
+  CertArgs a = cert_args(base + p.hdata.at, reinterpret_cast<const uint64_t*>(base + p.hoff.at), base + p.ids.at,
+                         base + p.origins.at, base + p.hsigs.at, reinterpret_cast<const uint64_t*>(base + p.rounds.at),
+                         base + p.vpks.at, base + p.vsigs.at, reinterpret_cast<const uint64_t*>(base + p.voff.at), nc,
+                         nv);
+  key_args(a, d, ks);
+  a.status = reinterpret_cast<uint32_t*>(base + p.status.at);
+  return a;
+}
+
+// Certificates [lo, hi) of `in` inline in ci's buffer (no pinned staging
+// copy, no H2D transfer); false when they do not fit (ci untouched).
 bool cert_inl_build(CertInl& ci, const CertIn& in, size_t lo, size_t hi) {
-  const size_t nc = hi - lo;
-  const uint64_t h0 = in.hdr_off[lo], hb = in.hdr_off[hi] - h0;
-  const uint64_t v0 = in.voff[lo], nv = in.voff[hi] - v0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 16);
-    return (uint32_t)at;
-  };
-  ci.off_hoff = take((nc + 1) * 8);
-  ci.off_voff = take((nc + 1) * 8);
-  ci.off_ids = take(nc * 32);
-  ci.off_origins = take(nc * 32);
-  ci.off_hsigs = take(nc * 64);
-  ci.off_rounds = take(nc * 8);
-  ci.off_vpks = take(nv * 32);
-  ci.off_vsigs = take(nv * 64);
-  ci.off_hdr = take(hb + 16);
-  if (o > COA_CERT_INLINE_BYTES || nc > 64) return false;
-  uint8_t* b = ci.buf;
-  uint64_t* ho = reinterpret_cast<uint64_t*>(b + ci.off_hoff);
-  uint64_t* vo = reinterpret_cast<uint64_t*>(b + ci.off_voff);
-  for (size_t i = 0; i <= nc; i++) {
-    ho[i] = in.hdr_off[lo + i] - h0;
-    vo[i] = in.voff[lo + i] - v0;
-  }
-  std::memcpy(b + ci.off_ids, in.ids + lo * 32, nc * 32);
-  std::memcpy(b + ci.off_origins, in.origins + lo * 32, nc * 32);
-  std::memcpy(b + ci.off_hsigs, in.hsigs + lo * 64, nc * 64);
-  std::memcpy(b + ci.off_rounds, in.rounds + lo, nc * 8);
-  if (nv) {
-    std::memcpy(b + ci.off_vpks, in.vpks + v0 * 32, nv * 32);
-    std::memcpy(b + ci.off_vsigs, in.vsigs + v0 * 64, nv * 64);
-  }
-  if (hb) std::memcpy(b + ci.off_hdr, in.hdr_data + h0, hb);
-  std::memset(b + ci.off_hdr + hb, 0, 16);
+  CertPack p;
+  if (!cert_inline_pack(ci.buf, COA_CERT_INLINE_BYTES, p, in, lo, hi)) return false;
+  ci.off_hoff = (uint32_t)p.hoff.at;
+  ci.off_voff = (uint32_t)p.voff.at;
+  ci.off_ids = (uint32_t)p.ids.at;
+  ci.off_origins = (uint32_t)p.origins.at;
+  ci.off_hsigs = (uint32_t)p.hsigs.at;
+  ci.off_rounds = (uint32_t)p.rounds.at;
+  ci.off_vpks = (uint32_t)p.vpks.at;
+  ci.off_vsigs = (uint32_t)p.vsigs.at;
+  ci.off_hdr = (uint32_t)p.hdata.at;
   return true;
 }
 
+// a's last block publishes nc status words into d.lat_res under a fresh tag.
+// d.lat_ctr is allocated on first use: [0] the latency kernels' block
+// counter, [1..64] status words; the kernel re-zeroes both.
+int cert_publish_prepare(Dev& d, hipStream_t s, size_t nc, CertArgs& a) {
+  if (!d.lat_ctr) {
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d.lat_ctr), 65 * 4));
+    HIP_TRY(hipMemsetAsync(d.lat_ctr, 0, 65 * 4, s));
+  }
+  const int rc = lat_res_prepare(d, nc, a.tag);  // may move d.lat_res
+  a.host_res = d.lat_res;
+  a.done_ctr = d.lat_ctr;
+  return rc;
+}
+
+// The latency launch with the certificates inline in the kernel arguments:
+// for calls whose arrays fit COA_CERT_INLINE_BYTES.  Returns 1 when they do
+// not fit (nothing launched).
 int cert_inline(Dev& d, const CertIn& in, size_t lo, size_t hi, uint32_t* status_out) {
   const size_t nc = hi - lo;
   const uint64_t nv = in.voff[hi] - in.voff[lo];
   static thread_local CertInl ci;  // ~3 KB, staged on the host; copied into the launch
   if (!cert_inl_build(ci, in, lo, hi)) return 1;
   hipStream_t s = d.stream;
-  if (!d.lat_ctr) {  // [0] block counter, [1..64] status words; the kernel re-zeroes both
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d.lat_ctr), 65 * 4));
-    HIP_TRY(hipMemsetAsync(d.lat_ctr, 0, 65 * 4, s));
-  }
-  uint32_t tag = 0;
-  int rc = lat_res_prepare(d, nc, tag);
-  if (rc != COA_OK) return rc;
   CertArgs& a = ci.a;
   const KeySetP ks = keys_now(d);  // held until the status words are in
-  a = cert_args(d, *ks, nullptr, CertPack{}, nc, nv);
+  a = cert_args_packed(d, *ks, nullptr, CertPack{}, nc, nv);
+  const int rc = cert_publish_prepare(d, s, nc, a);
+  if (rc != COA_OK) return rc;
   a.status = d.lat_ctr + 1;
-  a.host_res = d.lat_res;
-  a.done_ctr = d.lat_ctr;
-  a.tag = tag;
   HIP_TRY(coa_launch_cert_verify_inl(ci, s));
-  return lat_res_wait(d, s, nc, tag, status_out + lo);
+  return lat_res_wait(d, s, nc, a.tag, status_out + lo);
 }
 
-// Packs certificates [lo, hi) into page-locked staging h laid out as p (the
-// copies spread over the CopyPool).
-void cert_pack(uint8_t* h, const CertPack& p, const CertIn& in, size_t lo, size_t hi) {
-  const size_t nc = hi - lo;
-  const uint64_t h0 = in.hdr_off[lo], hb = in.hdr_off[hi] - h0;
-  const uint64_t v0 = in.voff[lo], nv = in.voff[hi] - v0;
-  std::memset(h + p.status, 0, nc * 4);
-  uint64_t* ho = reinterpret_cast<uint64_t*>(h + p.hoff);
-  uint64_t* vo = reinterpret_cast<uint64_t*>(h + p.voff);
-  for (size_t i = 0; i <= nc; i++) {
-    ho[i] = in.hdr_off[lo + i] - h0;
-    vo[i] = in.voff[lo + i] - v0;
-  }
-  std::vector<CopyPool::Seg> segs = {{h + p.ids, in.ids + lo * 32, nc * 32},
-                                     {h + p.origins, in.origins + lo * 32, nc * 32},
-                                     {h + p.hsigs, in.hsigs + lo * 64, nc * 64},
-                                     {h + p.rounds, in.rounds + lo, nc * 8}};
-  if (nv) {
-    segs.push_back({h + p.vpks, in.vpks + v0 * 32, nv * 32});
-    segs.push_back({h + p.vsigs, in.vsigs + v0 * 64, nv * 64});
-  }
-  if (hb) segs.push_back({h + p.hdata, in.hdr_data + h0, hb});
-  CopyPool::get().copy(segs);
+// What a verdict call adds to a shard: the payload counts (null for votes,
+// which have none).  The shard then decides the protocol checks of
+// coa_protocol.hip on its own stream, over the arrays its crypto launch
+// reads, and answers verdict words (include/coa_verify.h, COA_DAG_*) instead
+// of raw status words.
+struct ProtoIn {
+  const uint32_t* pcounts;
+};
+
+// The protocol table of generation ks (wanted false: a crypto-only shard
+// needs none).
+int prot_tab(bool wanted, const KeySet& ks, ProtTab& t) {
+  if (!wanted) return COA_OK;
+  if (!ks.has_prot) return fail(COA_EINVAL, "committee registered without stakes");
+  const uint32_t* w = ks.prot.as<uint32_t>();
+  t.keys = ks.ckeys.as<uint32_t>();
+  t.stake = w;
+  t.woff = w + ks.nkeys;
+  t.wids = w + 2 * (size_t)ks.nkeys + 1;
+  t.nk = ks.nkeys;
+  t.quorum = ks.quorum;
+  return COA_OK;
 }
 
 // Jobs (header + votes) per chunk of the pipelined certificate path
@@ -1431,37 +1388,93 @@ int cert_buffers() {
   return v < 2 ? 2 : (v > 4 ? 4 : v);
 }
 
+// One packed block of certificates: page-locked staging h, device copy base.
+struct CertBlock {
+  CertPack p;
+  size_t nc, nv;
+  uint8_t* h;
+  uint8_t* base;
+};
+
+// Packs certificates [lo, hi) into pin (the copies spread over the
+// CopyPool) for its device copy dev; pr: with the payload counts.
+int cert_pack(CertBlock& b, const CertIn& in, const ProtoIn* pr, size_t lo, size_t hi, PinBuf& pin, DevBuf& dev) {
+  b.nc = hi - lo;
+  b.nv = in.voff[hi] - in.voff[lo];
+  b.p = cert_layout(b.nc, b.nv, in.hdr_off[hi] - in.hdr_off[lo], pr != nullptr);
+  HIP_TRY(pin.ensure(b.p.total));
+  HIP_TRY(dev.ensure(b.p.total));
+  b.h = static_cast<uint8_t*>(pin.p);
+  b.base = dev.as<uint8_t>();
+  const SegList segs = cert_segments(b.h, b.p, in, pr ? pr->pcounts : nullptr, lo, hi);
+  CopyPool::get().copy(segs.s, segs.n);
+  return COA_OK;
+}
+
+// Block b's H2D copy, the crypto launch and, with a protocol table, the
+// protocol kernel and the merge, all on s; `words` is the section that then
+// holds the block's answer (status words, or verdict words with t).
+int cert_launch(const Dev& d, const KeySet& ks, const ProtTab* t, const CertBlock& b, int lanes, bool key_order,
+                uint32_t* scratch, hipStream_t s, Sec& words) {
+  const CertPack& p = b.p;
+  HIP_TRY(hipMemcpyAsync(b.base, b.h, p.total, hipMemcpyHostToDevice, s));
+  CertArgs a = cert_args_packed(d, ks, b.base, p, b.nc, b.nv);
+  a.key_order = key_order ? 1u : 0u;
+  HIP_TRY(coa_launch_cert_verify(a, lanes, scratch, s));
+  words = p.status;
+  if (!t) return COA_OK;
+  CertProtArgs q{};
+  q.hdr_data = a.hdr_data;
+  q.hdr_off = a.hdr_off;
+  q.ids = a.ids;
+  q.origins = a.origins;
+  q.rounds = a.rounds;
+  q.vpks = a.vpks;
+  q.voff = a.voff;
+  q.pcounts = reinterpret_cast<const uint32_t*>(b.base + p.pcounts.at);
+  q.nc = a.nc;
+  q.nv = a.nv;
+  q.proto = reinterpret_cast<uint32_t*>(b.base + p.proto.at);
+  HIP_TRY(coa_launch_cert_protocol(q, *t, s));
+  HIP_TRY(coa_launch_verdict_merge(a.status, q.proto, reinterpret_cast<uint32_t*>(b.base + p.verd.at), a.nc, s));
+  words = p.verd;
+  return COA_OK;
+}
+
+// A shard's answer: section `words` of device block base through its
+// staging h to out (one D2H), once the stream has drained.
+int read_back(uint8_t* h, const uint8_t* base, const Sec& words, uint32_t* out, hipStream_t s) {
+  HIP_TRY(hipMemcpyAsync(h + words.at, base + words.at, words.bytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(out, h + words.at, words.bytes);
+  return COA_OK;
+}
+
 // Certificates [lo, hi) on one device in chunks, up to cert_buffers() in
 // flight on as many streams, each with its own page-locked staging and
 // device buffers: while the GPU runs chunk k's kernel, chunk k + 1's copy
 // crosses PCIe and the host packs chunk k + 2 (CopyPool).  With two buffer
 // sets the host could only pack chunk k + 2 once chunk k had finished, so a
-// round took about (pack + copy + kernel) / 2 per chunk.  Raw status words
-// out.  COA_CERT_TRACE=1 prints the host's pack and wait time per call.
-int cert_shard_pipelined(Dev& d, const CertIn& in, size_t lo, size_t hi, uint32_t* status_out) {
-  const size_t chunk_jobs = cert_chunk_jobs();
+// round took about (pack + copy + kernel) / 2 per chunk.  Answer words as
+// cert_shard's (a chunk ends between certificates, and a verdict word's vote
+// index is relative to its certificate, so chunking does not change them).
+// COA_CERT_TRACE=1 prints the host's pack and wait time per call.
+int cert_shard_pipelined(Dev& d, const CertIn& in, const ProtoIn* pr, size_t lo, size_t hi, uint32_t* out) {
   const int nb = cert_buffers();
-  const int ramp = cert_ramp();
-  std::vector<size_t> cuts{lo};
-  size_t jobs = 0;
-  for (size_t c = lo; c < hi; c++) {
-    jobs += 1 + (in.voff[c + 1] - in.voff[c]);
-    const int k = (int)cuts.size() - 1;  // the chunk being cut
-    if (jobs >= (chunk_jobs >> std::max(0, ramp - k)) && c + 1 < hi) {
-      cuts.push_back(c + 1);
-      jobs = 0;
-    }
-  }
-  cuts.push_back(hi);
+  const std::vector<size_t> cuts = cert_chunk_cuts(in.voff, lo, hi, cert_chunk_jobs(), cert_ramp());
   hipStream_t st[4] = {d.stream, nullptr, nullptr, nullptr};
   for (int b = 1; b < nb; b++) {
     if (!d.cstreams[b - 1]) HIP_TRY(hipStreamCreateWithFlags(&d.cstreams[b - 1], hipStreamNonBlocking));
     st[b] = d.cstreams[b - 1];
   }
   const KeySetP ks = keys_now(d);  // held until every chunk is done
+  ProtTab t;
+  int rc = prot_tab(pr != nullptr, *ks, t);
+  if (rc != COA_OK) return rc;
   struct Pending {
     bool busy = false;
-    size_t lo = 0, hi = 0, status = 0;
+    size_t lo = 0;
+    Sec words;
   } pend[4];
   const bool trace = env_is("COA_CERT_TRACE", "1");
   double t_pack = 0, t_wait = 0;
@@ -1471,34 +1484,29 @@ int cert_shard_pipelined(Dev& d, const CertIn& in, size_t lo, size_t hi, uint32_
     const double t0 = trace ? now() : 0;
     HIP_TRY(hipStreamSynchronize(st[b]));
     if (trace) t_wait += now() - t0;
-    std::memcpy(status_out + pend[b].lo, static_cast<uint8_t*>(d.pinc[b].p) + pend[b].status,
-                (pend[b].hi - pend[b].lo) * 4);
+    std::memcpy(out + pend[b].lo, static_cast<uint8_t*>(d.pinc[b].p) + pend[b].words.at, pend[b].words.bytes);
     pend[b].busy = false;
     return COA_OK;
   };
   for (size_t k = 0; k + 1 < cuts.size(); k++) {
     const int b = (int)(k % nb);
-    int rc = drain(b);  // this buffer set's previous chunk
+    rc = drain(b);  // this buffer set's previous chunk
     if (rc != COA_OK) return rc;
-    const size_t clo = cuts[k], chi = cuts[k + 1], nc = chi - clo;
-    const uint64_t nv = in.voff[chi] - in.voff[clo], hb = in.hdr_off[chi] - in.hdr_off[clo];
-    const CertPack p = cert_layout(nc, nv, hb);
-    HIP_TRY(d.pinc[b].ensure(p.total));
-    HIP_TRY(d.certc[b].ensure(p.total));
-    HIP_TRY(d.cscrc[b].ensure(coa_cert_scratch_bytes(nc + nv, pipe_keysort())));
-    uint8_t* h = static_cast<uint8_t*>(d.pinc[b].p);
+    const size_t clo = cuts[k], chi = cuts[k + 1];
     const double t0 = trace ? now() : 0;
-    cert_pack(h, p, in, clo, chi);
+    CertBlock blk;
+    rc = cert_pack(blk, in, pr, clo, chi, d.pinc[b], d.certc[b]);
+    if (rc != COA_OK) return rc;
     if (trace) t_pack += now() - t0;
-    HIP_TRY(hipMemcpyAsync(d.certc[b].p, h, p.total, hipMemcpyHostToDevice, st[b]));
-    CertArgs a = cert_args(d, *ks, d.certc[b].as<uint8_t>(), p, nc, nv);
-    a.key_order = pipe_keysort() ? 1u : 0u;
-    HIP_TRY(coa_launch_cert_verify(a, 1, d.cscrc[b].as<uint32_t>(), st[b]));
-    HIP_TRY(hipMemcpyAsync(h + p.status, d.certc[b].as<uint8_t>() + p.status, nc * 4, hipMemcpyDeviceToHost, st[b]));
-    pend[b] = {true, clo, chi, p.status};
+    HIP_TRY(d.cscrc[b].ensure(coa_cert_scratch_bytes(blk.nc + blk.nv, pipe_keysort())));
+    Sec words;
+    rc = cert_launch(d, *ks, pr ? &t : nullptr, blk, 1, pipe_keysort(), d.cscrc[b].as<uint32_t>(), st[b], words);
+    if (rc != COA_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(blk.h + words.at, blk.base + words.at, words.bytes, hipMemcpyDeviceToHost, st[b]));
+    pend[b] = {true, clo, words};
   }
   for (size_t k = 0; k < (size_t)nb; k++) {
-    const int rc = drain((int)((cuts.size() - 1 + k) % nb));  // oldest first
+    rc = drain((int)((cuts.size() - 1 + k) % nb));  // oldest first
     if (rc != COA_OK) return rc;
   }
   if (trace)
@@ -1507,46 +1515,43 @@ int cert_shard_pipelined(Dev& d, const CertIn& in, size_t lo, size_t hi, uint32_
   return COA_OK;
 }
 
-int cert_shard(Dev& d, const CertIn& in, size_t lo, size_t hi, uint32_t* status_out, bool publish = false) {
+// Fast path for certificates [lo, hi) on one device (its lock held): raw
+// status words out, or with pr their verdict words.  publish: the latency
+// variant writes its status words straight into page-locked host memory (no
+// D2H copy, no stream synchronisation).
+int cert_shard(Dev& d, const CertIn& in, const ProtoIn* pr, size_t lo, size_t hi, uint32_t* out,
+               bool publish = false) {
   const size_t nc = hi - lo;
-  const uint64_t h0 = in.hdr_off[lo], hb = in.hdr_off[hi] - h0;
-  const uint64_t v0 = in.voff[lo], nv = in.voff[hi] - v0;
-  if (publish && cert_lanes(nc + nv) == 64 && !env_is("COA_CERT_INLINE", "0")) {
-    const int rc = cert_inline(d, in, lo, hi, status_out);
+  const uint64_t nv = in.voff[hi] - in.voff[lo];
+  const int lanes = cert_lanes(nc + nv);
+  publish = publish && lanes == 64;
+  if (publish && !env_is("COA_CERT_INLINE", "0")) {
+    const int rc = cert_inline(d, in, lo, hi, out);
     if (rc != 1) return rc;
   }
   if (!publish && nc + nv >= 2 * cert_chunk_jobs() && !env_is("COA_CERT_PIPELINE", "0"))
-    return cert_shard_pipelined(d, in, lo, hi, status_out);
-  const CertPack p = cert_layout(nc, nv, hb);
-  HIP_TRY(d.pin.ensure(p.total));
-  HIP_TRY(d.cert.ensure(p.total));
-  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
-  cert_pack(h, p, in, lo, hi);
+    return cert_shard_pipelined(d, in, pr, lo, hi, out);
+  const KeySetP ks = keys_now(d);  // held until the answer words are in
+  ProtTab t;
+  int rc = prot_tab(pr != nullptr, *ks, t);
+  if (rc != COA_OK) return rc;
+  CertBlock b;
+  rc = cert_pack(b, in, pr, lo, hi, d.pin, d.cert);
+  if (rc != COA_OK) return rc;
   hipStream_t s = d.stream;
-  HIP_TRY(hipMemcpyAsync(d.cert.p, h, p.total, hipMemcpyHostToDevice, s));
-  const KeySetP ks = keys_now(d);  // held until the status words are in
-  CertArgs a = cert_args(d, *ks, d.cert.as<uint8_t>(), p, nc, nv);
-  const int lanes = cert_lanes(nc + nv);
-  if (lanes == 64 && publish) {  // the last block writes the status words to host memory
-    if (!d.lat_ctr) {
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d.lat_ctr), 65 * 4));
-      HIP_TRY(hipMemsetAsync(d.lat_ctr, 0, 65 * 4, s));
-    }
-    uint32_t tag = 0;
-    int rc = lat_res_prepare(d, nc, tag);
+  if (publish) {  // the last block writes the status words to host memory
+    HIP_TRY(hipMemcpyAsync(b.base, b.h, b.p.total, hipMemcpyHostToDevice, s));
+    CertArgs a = cert_args_packed(d, *ks, b.base, b.p, nc, nv);
+    rc = cert_publish_prepare(d, s, nc, a);
     if (rc != COA_OK) return rc;
-    a.host_res = d.lat_res;
-    a.done_ctr = d.lat_ctr;
-    a.tag = tag;
     HIP_TRY(coa_launch_cert_verify(a, lanes, nullptr, s));
-    return lat_res_wait(d, s, nc, tag, status_out + lo);
+    return lat_res_wait(d, s, nc, a.tag, out + lo);
   }
-  if (lanes == 1) HIP_TRY(d.cscr.ensure(coa_cert_scratch_bytes(nc + nv, a.key_order != 0)));
-  HIP_TRY(coa_launch_cert_verify(a, lanes, d.cscr.as<uint32_t>(), s));
-  HIP_TRY(hipMemcpyAsync(h + p.status, d.cert.as<uint8_t>() + p.status, nc * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(status_out + lo, h + p.status, nc * 4);
-  return COA_OK;
+  if (lanes == 1) HIP_TRY(d.cscr.ensure(coa_cert_scratch_bytes(nc + nv, false)));
+  Sec words;
+  rc = cert_launch(d, *ks, pr ? &t : nullptr, b, lanes, false, d.cscr.as<uint32_t>(), s, words);
+  if (rc != COA_OK) return rc;
+  return read_back(b.h, b.base, words, out + lo, s);
 }
 
 // Exact (non-cached) resolution of certificates `idx`: header signatures by
@@ -1689,9 +1694,10 @@ int resolve_raw(const CertIn& in, size_t n, uint32_t* st, uint64_t rng_seed) {
   return cert_resolve(in, rlc, false, seed, st);
 }
 
-int certificates_impl(const CertIn& in, size_t n, uint64_t rng_seed, uint8_t* status_out) {
-  if (n == 0) return COA_OK;
-  if (!in.hdr_off || !in.ids || !in.origins || !in.hsigs || !in.rounds || !in.voff || !status_out)
+// The argument checks of the host-pointer certificate calls (out: the call's
+// output array).
+int cert_in_check(const CertIn& in, size_t n, const void* out) {
+  if (!in.hdr_off || !in.ids || !in.origins || !in.hsigs || !in.rounds || !in.voff || !out)
     return fail(COA_EINVAL, "null argument");
   for (size_t i = 0; i < n; i++)
     if (in.hdr_off[i + 1] < in.hdr_off[i] || in.voff[i + 1] < in.voff[i])
@@ -1699,17 +1705,22 @@ int certificates_impl(const CertIn& in, size_t n, uint64_t rng_seed, uint8_t* st
   if (in.voff[0] != 0) return fail(COA_EINVAL, "vote_offsets[0] must be 0");
   if (in.hdr_off[n] > in.hdr_off[0] && !in.hdr_data) return fail(COA_EINVAL, "null header data");
   if (in.voff[n] && (!in.vpks || !in.vsigs)) return fail(COA_EINVAL, "null vote arrays");
-  if (check_n(n + in.voff[n]) != COA_OK) return COA_EINVAL;
+  return check_n(n + in.voff[n]);
+}
+
+int certificates_impl(const CertIn& in, size_t n, uint64_t rng_seed, uint8_t* status_out) {
+  if (n == 0) return COA_OK;
+  int rc = cert_in_check(in, n, status_out);
+  if (rc != COA_OK) return rc;
   std::vector<uint32_t> st(n, 0);
-  int rc;
   if (cert_lanes(n + in.voff[n]) == 64) {  // latency path: one idle context, no stream sync
     std::unique_lock<std::mutex> l;
     Dev& d = lat_dev(l);
     HIP_TRY(hipSetDevice(d.id));
-    rc = cert_shard(d, in, 0, n, st.data(), true);
+    rc = cert_shard(d, in, nullptr, 0, n, st.data(), true);
   } else {
     rc = for_shards(
-        n, [&](Dev& d, size_t lo, size_t hi) -> int { return cert_shard(d, in, lo, hi, st.data()); },
+        n, [&](Dev& d, size_t lo, size_t hi) -> int { return cert_shard(d, in, nullptr, lo, hi, st.data()); },
         n + in.voff[n]);
   }
   if (rc != COA_OK) return rc;
@@ -1723,100 +1734,60 @@ int certificates_impl(const CertIn& in, size_t n, uint64_t rng_seed, uint8_t* st
 // Header::verify / Vote::verify crypto for many messages (k_msg_verify).  A
 // shard [lo, hi) is packed into the context's pinned staging and copied with
 // ONE H2D; the raw status words come back with one D2H.
-struct MsgIn {
-  const uint8_t* hdr_data;  // headers only
-  const uint64_t* hdr_off;  // headers only
-  const uint8_t* ids;
-  const uint64_t* rounds;   // votes only
-  const uint8_t* origins;   // votes only
-  const uint8_t* authors;
-  const uint8_t* sigs;
-  bool votes;
-};
-
-struct MsgPack {
-  size_t status, ids, authors, sigs, rounds, origins, hoff, hdata, total;
-};
-MsgPack msg_layout(size_t n, bool votes, size_t hbytes) {
-  MsgPack p{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  p.status = take(n * 4);
-  p.ids = take(n * 32);
-  p.authors = take(n * 32);
-  p.sigs = take(n * 64);
-  if (votes) {
-    p.rounds = take(n * 8);
-    p.origins = take(n * 32);
-  } else {
-    p.hoff = take((n + 1) * 8);
-    p.hdata = take(hbytes + 16);
-  }
-  p.total = o;
-  return p;
+// The arrays of a message launch, device pointers (hdr_* null: votes; rounds
+// and origins null: headers); the key tables are the caller's to set.
+MsgArgs msg_args(const uint8_t* hdr_data, const uint64_t* hdr_off, const uint8_t* ids, const uint64_t* rounds,
+                 const uint8_t* origins, const uint8_t* authors, const uint8_t* sigs, size_t n, uint32_t* status) {
+  MsgArgs a{};
+  a.hdr_data = hdr_data;
+  a.hdr_off = hdr_off;
+  a.ids = reinterpret_cast<const uint32_t*>(ids);
+  a.rounds = rounds;
+  a.origins = reinterpret_cast<const uint32_t*>(origins);
+  a.authors = reinterpret_cast<const uint32_t*>(authors);
+  a.sigs = reinterpret_cast<const uint32_t*>(sigs);
+  a.n = (uint32_t)n;
+  a.status = status;
+  return a;
 }
 
-// the key tables of generation ks and context d's fixed-base combs
-void msg_key_args(MsgArgs& a, Dev& d, const KeySet& ks) {
-  a.keys = ks.ckeys.as<uint32_t>();
-  a.kflags = ks.kflags.as<uint32_t>();
-  a.ktabs = ks.ktabs.as<uint32_t>();
-  a.nk = ks.nkeys;
-  a.comb = d.comb;
-  a.wcomb = wcomb_of(d);
-  a.kwtabs = (ks.kwide && !env_is("COA_KEY_WCOMB", "0")) ? ks.kwtabs.as<uint32_t>() : nullptr;
-  a.kw20 = ks.kw20 ? 1u : 0u;
-}
-
-// Messages [lo, hi) on one context (its lock held): raw status words out.
-int msg_shard(Dev& d, const MsgIn& in, size_t lo, size_t hi, uint32_t* raw) {
+// Messages [lo, hi) on one context (its lock held): raw status words out, or
+// with pr their verdict words (cert_shard's protocol tail, for messages).
+int msg_shard(Dev& d, const MsgIn& in, const ProtoIn* pr, size_t lo, size_t hi, uint32_t* out) {
   const size_t n = hi - lo;
-  const uint64_t h0 = in.votes ? 0 : in.hdr_off[lo], hb = in.votes ? 0 : in.hdr_off[hi] - h0;
-  const MsgPack p = msg_layout(n, in.votes, hb);
+  const KeySetP ks = keys_now(d);  // held until the answer words are in
+  ProtTab t;
+  const int rc = prot_tab(pr != nullptr, *ks, t);
+  if (rc != COA_OK) return rc;
+  const MsgPack p = msg_layout(n, in.votes, in.votes ? 0 : in.hdr_off[hi] - in.hdr_off[lo], pr != nullptr);
   HIP_TRY(d.pin.ensure(p.total));
   HIP_TRY(d.cert.ensure(p.total));
   HIP_TRY(d.cscr.ensure(coa_msg_scratch_bytes(n)));
   uint8_t* h = static_cast<uint8_t*>(d.pin.p);
-  std::memset(h + p.status, 0, n * 4);
-  std::vector<CopyPool::Seg> segs = {{h + p.ids, in.ids + lo * 32, n * 32},
-                                     {h + p.authors, in.authors + lo * 32, n * 32},
-                                     {h + p.sigs, in.sigs + lo * 64, n * 64}};
-  if (in.votes) {
-    segs.push_back({h + p.rounds, in.rounds + lo, n * 8});
-    segs.push_back({h + p.origins, in.origins + lo * 32, n * 32});
-  } else {
-    uint64_t* ho = reinterpret_cast<uint64_t*>(h + p.hoff);
-    for (size_t i = 0; i <= n; i++) ho[i] = in.hdr_off[lo + i] - h0;
-    if (hb) segs.push_back({h + p.hdata, in.hdr_data + h0, hb});
-  }
-  CopyPool::get().copy(segs);
+  const SegList segs = msg_segments(h, p, in, pr ? pr->pcounts : nullptr, lo, hi);
+  CopyPool::get().copy(segs.s, segs.n);
   hipStream_t s = d.stream;
   uint8_t* base = d.cert.as<uint8_t>();
   HIP_TRY(hipMemcpyAsync(base, h, p.total, hipMemcpyHostToDevice, s));
-  const KeySetP ks = keys_now(d);  // held until the status words are in
-  MsgArgs a{};
-  a.ids = reinterpret_cast<const uint32_t*>(base + p.ids);
-  a.authors = reinterpret_cast<const uint32_t*>(base + p.authors);
-  a.sigs = reinterpret_cast<const uint32_t*>(base + p.sigs);
-  if (in.votes) {
-    a.rounds = reinterpret_cast<const uint64_t*>(base + p.rounds);
-    a.origins = reinterpret_cast<const uint32_t*>(base + p.origins);
-  } else {
-    a.hdr_data = base + p.hdata;
-    a.hdr_off = reinterpret_cast<const uint64_t*>(base + p.hoff);
-  }
-  a.n = (uint32_t)n;
-  msg_key_args(a, d, *ks);
-  a.status = reinterpret_cast<uint32_t*>(base + p.status);
+  const uint8_t* none = nullptr;  // the other shape's arrays
+  MsgArgs a = msg_args(in.votes ? none : base + p.hdata.at,
+                       reinterpret_cast<const uint64_t*>(in.votes ? none : base + p.hoff.at), base + p.ids.at,
+                       reinterpret_cast<const uint64_t*>(in.votes ? base + p.rounds.at : none),
+                       in.votes ? base + p.origins.at : none, base + p.authors.at, base + p.sigs.at, n,
+                       reinterpret_cast<uint32_t*>(base + p.status.at));
+  key_args(a, d, *ks);
   HIP_TRY(coa_launch_msg_verify(a, d.cscr.as<uint32_t>(), s));
-  HIP_TRY(hipMemcpyAsync(h + p.status, base + p.status, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(raw + lo, h + p.status, n * 4);
-  return COA_OK;
+  if (!pr) return read_back(h, base, p.status, out + lo, s);
+  MsgProtArgs q{};
+  q.hdr_data = a.hdr_data;
+  q.hdr_off = a.hdr_off;
+  if (!in.votes) q.pcounts = reinterpret_cast<const uint32_t*>(base + p.pcounts.at);
+  q.authors = a.authors;
+  q.n = a.n;
+  q.proto = reinterpret_cast<uint32_t*>(base + p.proto.at);
+  HIP_TRY(coa_launch_msg_protocol(q, t, s));
+  HIP_TRY(coa_launch_verdict_merge(a.status, q.proto, reinterpret_cast<uint32_t*>(base + p.verd.at), a.n, s));
+  return read_back(h, base, p.verd, out + lo, s);
 }
 
 // Raw words of all n messages, then the exact re-decision of the items whose
@@ -1826,7 +1797,7 @@ int msg_shard(Dev& d, const MsgIn& in, size_t lo, size_t hi, uint32_t* raw) {
 int messages_resolve(const MsgIn& in, size_t n, uint32_t* st);
 int messages_impl(const MsgIn& in, size_t n, std::vector<uint32_t>& st) {
   st.assign(n, 0);
-  int rc = for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int { return msg_shard(d, in, lo, hi, st.data()); });
+  int rc = for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int { return msg_shard(d, in, nullptr, lo, hi, st.data()); });
   if (rc != COA_OK) return rc;
   return messages_resolve(in, n, st.data());
 }
@@ -1875,7 +1846,7 @@ int messages_device(int device, MsgArgs a, void* workspace, void* stream) {
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = stream ? (hipStream_t)stream : d->stream;
   const KeySetP ks = keys_now(*d);  // pinned (the queue) or current
-  msg_key_args(a, *d, *ks);
+  key_args(a, *d, *ks);
   HIP_TRY(hipMemsetAsync(a.status, 0, (size_t)a.n * 4, s));
   if (workspace) {
     HIP_TRY(coa_launch_msg_verify(a, static_cast<uint32_t*>(workspace), s));
@@ -1891,10 +1862,16 @@ int messages_device(int device, MsgArgs a, void* workspace, void* stream) {
 // ------------------------------------------------------------------------
 // Verdicts: the crypto status words above merged on the device with the
 // protocol checks of coa_protocol.hip (include/coa_verify.h, COA_DAG_*).
+// The host-pointer forms are the crypto shards with their protocol tail.
+int message_verdicts(const MsgIn& in, const uint32_t* pcounts, size_t n, uint32_t* out) {
+  const ProtoIn pr{pcounts};
+  return for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int { return msg_shard(d, in, &pr, lo, hi, out); });
+}
 
 // This thread's launches read generation `ks` for the scope's lifetime, so
-// the crypto launch and the protocol launch of one verdict call see the same
-// committee (a pin the aggregation queue set stays as it is).
+// the crypto launch and the protocol launch of one device-resident verdict
+// call see the same committee (a pin the aggregation queue set stays as it
+// is).
 struct KeyScope {
   const KeySetP* prev;
   explicit KeyScope(const KeySetP& ks) : prev(t_keys_pinned) {
@@ -1902,143 +1879,6 @@ struct KeyScope {
   }
   ~KeyScope() { t_keys_pinned = prev; }
 };
-
-int prot_tab(const KeySet& ks, ProtTab& t) {
-  if (!ks.has_prot) return fail(COA_EINVAL, "committee registered without stakes");
-  const uint32_t* w = ks.prot.as<uint32_t>();
-  t.keys = ks.ckeys.as<uint32_t>();
-  t.stake = w;
-  t.woff = w + ks.nkeys;
-  t.wids = w + 2 * (size_t)ks.nkeys + 1;
-  t.nk = ks.nkeys;
-  t.quorum = ks.quorum;
-  return COA_OK;
-}
-
-// Certificates [lo, hi) on one context (its lock held): the raw status words
-// of the crypto path, then the protocol kernel and the merge over the arrays
-// those read (one more H2D: no signatures), verdict words out.
-int verdict_cert_shard(Dev& d, const CertIn& in, const uint32_t* pcounts, size_t lo, size_t hi, uint32_t* raw,
-                       uint32_t* out) {
-  const KeySetP ks = keys_now(d);
-  ProtTab t;
-  int rc = prot_tab(*ks, t);
-  if (rc != COA_OK) return rc;
-  const KeyScope scope(ks);
-  rc = cert_shard(d, in, lo, hi, raw);
-  if (rc != COA_OK) return rc;
-  const size_t nc = hi - lo;
-  const uint64_t h0 = in.hdr_off[lo], hb = in.hdr_off[hi] - h0;
-  const uint64_t v0 = in.voff[lo], nv = in.voff[hi] - v0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  const size_t p_verd = take(nc * 4), p_raw = take(nc * 4), p_proto = take(nc * 4), p_pc = take(nc * 4),
-               p_hoff = take((nc + 1) * 8), p_voff = take((nc + 1) * 8), p_rounds = take(nc * 8),
-               p_ids = take(nc * 32), p_origins = take(nc * 32), p_vpks = take(nv * 32), p_hdata = take(hb + 16);
-  HIP_TRY(d.pin.ensure(o));
-  HIP_TRY(d.cert.ensure(o));
-  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
-  uint64_t* ho = reinterpret_cast<uint64_t*>(h + p_hoff);
-  uint64_t* vo = reinterpret_cast<uint64_t*>(h + p_voff);
-  for (size_t i = 0; i <= nc; i++) {
-    ho[i] = in.hdr_off[lo + i] - h0;
-    vo[i] = in.voff[lo + i] - v0;
-  }
-  std::vector<CopyPool::Seg> segs = {{h + p_raw, raw + lo, nc * 4},
-                                     {h + p_pc, pcounts + lo, nc * 4},
-                                     {h + p_rounds, in.rounds + lo, nc * 8},
-                                     {h + p_ids, in.ids + lo * 32, nc * 32},
-                                     {h + p_origins, in.origins + lo * 32, nc * 32}};
-  if (nv) segs.push_back({h + p_vpks, in.vpks + v0 * 32, nv * 32});
-  if (hb) segs.push_back({h + p_hdata, in.hdr_data + h0, hb});
-  CopyPool::get().copy(segs);
-  hipStream_t s = d.stream;
-  uint8_t* base = d.cert.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(base + p_raw, h + p_raw, o - p_raw, hipMemcpyHostToDevice, s));
-  CertProtArgs a{};
-  a.hdr_data = base + p_hdata;
-  a.hdr_off = reinterpret_cast<const uint64_t*>(base + p_hoff);
-  a.ids = reinterpret_cast<const uint32_t*>(base + p_ids);
-  a.origins = reinterpret_cast<const uint32_t*>(base + p_origins);
-  a.rounds = reinterpret_cast<const uint64_t*>(base + p_rounds);
-  a.vpks = reinterpret_cast<const uint32_t*>(base + p_vpks);
-  a.voff = reinterpret_cast<const uint64_t*>(base + p_voff);
-  a.pcounts = reinterpret_cast<const uint32_t*>(base + p_pc);
-  a.nc = (uint32_t)nc;
-  a.nv = (uint32_t)nv;
-  a.proto = reinterpret_cast<uint32_t*>(base + p_proto);
-  HIP_TRY(coa_launch_cert_protocol(a, t, s));
-  HIP_TRY(coa_launch_verdict_merge(reinterpret_cast<const uint32_t*>(base + p_raw), a.proto,
-                                   reinterpret_cast<uint32_t*>(base + p_verd), (uint32_t)nc, s));
-  HIP_TRY(hipMemcpyAsync(h + p_verd, base + p_verd, nc * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(out + lo, h + p_verd, nc * 4);
-  return COA_OK;
-}
-
-// The same for headers and votes.
-int verdict_msg_shard(Dev& d, const MsgIn& in, const uint32_t* pcounts, size_t lo, size_t hi, uint32_t* raw,
-                      uint32_t* out) {
-  const KeySetP ks = keys_now(d);
-  ProtTab t;
-  int rc = prot_tab(*ks, t);
-  if (rc != COA_OK) return rc;
-  const KeyScope scope(ks);
-  rc = msg_shard(d, in, lo, hi, raw);
-  if (rc != COA_OK) return rc;
-  const size_t n = hi - lo;
-  const uint64_t h0 = in.votes ? 0 : in.hdr_off[lo], hb = in.votes ? 0 : in.hdr_off[hi] - h0;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align_up(o + bytes, 256);
-    return at;
-  };
-  const size_t p_verd = take(n * 4), p_raw = take(n * 4), p_proto = take(n * 4), p_authors = take(n * 32),
-               p_pc = take(in.votes ? 0 : n * 4), p_hoff = take(in.votes ? 0 : (n + 1) * 8),
-               p_hdata = take(in.votes ? 0 : hb + 16);
-  HIP_TRY(d.pin.ensure(o));
-  HIP_TRY(d.cert.ensure(o));
-  uint8_t* h = static_cast<uint8_t*>(d.pin.p);
-  std::vector<CopyPool::Seg> segs = {{h + p_raw, raw + lo, n * 4}, {h + p_authors, in.authors + lo * 32, n * 32}};
-  if (!in.votes) {
-    uint64_t* ho = reinterpret_cast<uint64_t*>(h + p_hoff);
-    for (size_t i = 0; i <= n; i++) ho[i] = in.hdr_off[lo + i] - h0;
-    segs.push_back({h + p_pc, pcounts + lo, n * 4});
-    if (hb) segs.push_back({h + p_hdata, in.hdr_data + h0, hb});
-  }
-  CopyPool::get().copy(segs);
-  hipStream_t s = d.stream;
-  uint8_t* base = d.cert.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(base + p_raw, h + p_raw, o - p_raw, hipMemcpyHostToDevice, s));
-  MsgProtArgs a{};
-  if (!in.votes) {
-    a.hdr_data = base + p_hdata;
-    a.hdr_off = reinterpret_cast<const uint64_t*>(base + p_hoff);
-    a.pcounts = reinterpret_cast<const uint32_t*>(base + p_pc);
-  }
-  a.authors = reinterpret_cast<const uint32_t*>(base + p_authors);
-  a.n = (uint32_t)n;
-  a.proto = reinterpret_cast<uint32_t*>(base + p_proto);
-  HIP_TRY(coa_launch_msg_protocol(a, t, s));
-  HIP_TRY(coa_launch_verdict_merge(reinterpret_cast<const uint32_t*>(base + p_raw), a.proto,
-                                   reinterpret_cast<uint32_t*>(base + p_verd), (uint32_t)n, s));
-  HIP_TRY(hipMemcpyAsync(h + p_verd, base + p_verd, n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(out + lo, h + p_verd, n * 4);
-  return COA_OK;
-}
-
-int message_verdicts(const MsgIn& in, const uint32_t* pcounts, size_t n, uint32_t* out) {
-  std::vector<uint32_t> raw(n, 0);
-  return for_shards(n, [&](Dev& d, size_t lo, size_t hi) -> int {
-    return verdict_msg_shard(d, in, pcounts, lo, hi, raw.data(), out);
-  });
-}
 
 // Device-resident verdict calls: `crypto` enqueues the *_verify_many_device
 // launch with its raw words at `raw` and its workspace at `ws`; the protocol
@@ -2055,7 +1895,7 @@ int verdicts_device(int device, size_t n, size_t crypto_bytes, uint32_t* d_verdi
   hipStream_t s = stream ? (hipStream_t)stream : d->stream;
   const KeySetP ks = keys_now(*d);
   ProtTab t;
-  int rc = prot_tab(*ks, t);
+  int rc = prot_tab(true, *ks, t);
   if (rc != COA_OK) return rc;
   std::unique_lock<std::mutex> own;
   if (!workspace) {
@@ -2716,7 +2556,7 @@ void coa_keycache_unpin(void* pin) { delete static_cast<KeySetP*>(pin); }
 void coa_keycache_use(void* pin) { t_keys_pinned = static_cast<const KeySetP*>(pin); }
 
 void coa_copy_segments(const CoaCopySeg* segs, size_t n) {
-  std::vector<CopyPool::Seg> v;
+  std::vector<Seg> v;
   v.reserve(n);
   for (size_t i = 0; i < n; i++) v.push_back({segs[i].dst, segs[i].src, segs[i].bytes});
   CopyPool::get().copy(v);
@@ -2743,11 +2583,7 @@ int coa_lat_verify_device(int device, const uint8_t* d_in, size_t n, uint32_t* d
   // the pinned generation (the queue) or the current one: a registration
   // frees a replaced generation only after the device has drained
   const KeySetP ks = keys_now(*d);
-  a.keys = ks->ckeys.as<uint32_t>();
-  a.kflags = ks->kflags.as<uint32_t>();
-  a.ktabs = ks->ktabs.as<uint32_t>();
-  a.nk = ks->nkeys;
-  a.comb = d->comb;
+  key_args(a, *d, *ks);
   const hipStream_t s = stream ? (hipStream_t)stream : d->stream;
   HIP_TRY(coa_launch_verify_lat(a, s));
   return trail_keys(*d, ks, s);
@@ -2769,11 +2605,7 @@ int coa_lat_verify_inline(int device, const uint8_t* h_records, size_t n, uint32
   a.res = res;
   a.tag = tag;
   const KeySetP ks = keys_now(*d);  // pinned (the queue) or current; see coa_lat_verify_device
-  a.keys = ks->ckeys.as<uint32_t>();
-  a.kflags = ks->kflags.as<uint32_t>();
-  a.ktabs = ks->ktabs.as<uint32_t>();
-  a.nk = ks->nkeys;
-  a.comb = d->comb;
+  key_args(a, *d, *ks);
   const hipStream_t s = stream ? (hipStream_t)stream : d->stream;
   HIP_TRY(coa_launch_verify_lat(a, s));
   return trail_keys(*d, ks, s);
@@ -2804,7 +2636,7 @@ int coa_certificate_verify_publish(int device, const uint8_t* h_base, uint8_t* d
   static thread_local CertInl ci;
   if (!env_is("COA_CERT_INLINE", "0") && cert_inl_build(ci, in, 0, n)) {
     CertArgs& a = ci.a;
-    a = cert_args(*d, *ks, nullptr, CertPack{}, n, n_votes);
+    a = cert_args_packed(*d, *ks, nullptr, CertPack{}, n, n_votes);
     a.status = d_ctr + 1;
     a.host_res = host_res;
     a.done_ctr = d_ctr;
@@ -2813,17 +2645,11 @@ int coa_certificate_verify_publish(int device, const uint8_t* h_base, uint8_t* d
     return trail_keys(*d, ks, s);
   }
   HIP_TRY(hipMemcpyAsync(d_base, h_base, in_bytes, hipMemcpyHostToDevice, s));
-  CertPack p{};
-  p.hdata = off->hdr;
-  p.hoff = off->hoff;
-  p.ids = off->ids;
-  p.origins = off->origins;
-  p.hsigs = off->hsigs;
-  p.rounds = off->rounds;
-  p.vpks = off->vpks;
-  p.vsigs = off->vsigs;
-  p.voff = off->voff;
-  CertArgs a = cert_args(*d, *ks, d_base, p, n, n_votes);
+  CertArgs a = cert_args(d_base + off->hdr, reinterpret_cast<const uint64_t*>(d_base + off->hoff), d_base + off->ids,
+                         d_base + off->origins, d_base + off->hsigs,
+                         reinterpret_cast<const uint64_t*>(d_base + off->rounds), d_base + off->vpks,
+                         d_base + off->vsigs, reinterpret_cast<const uint64_t*>(d_base + off->voff), n, n_votes);
+  key_args(a, *d, *ks);
   a.status = d_ctr + 1;
   a.host_res = host_res;
   a.done_ctr = d_ctr;
@@ -2925,28 +2751,10 @@ int coa_certificate_verify_many_device_order(int device, const uint8_t* d_header
   if (!d) return fail(COA_EINVAL, "device not opened by coa_init");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  CertArgs a;
-  a.hdr_data = d_header_data;
-  a.hdr_off = d_header_offsets;
-  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
-  a.origins = reinterpret_cast<const uint32_t*>(d_origins);
-  a.hsigs = reinterpret_cast<const uint32_t*>(d_header_sigs);
-  a.rounds = d_rounds;
-  a.vpks = reinterpret_cast<const uint32_t*>(d_vote_pks);
-  a.vsigs = reinterpret_cast<const uint32_t*>(d_vote_sigs);
-  a.voff = d_vote_offsets;
-  a.nc = (uint32_t)n;
-  a.nv = (uint32_t)n_votes;
-  a.hdr_blocks = 0;
+  CertArgs a = cert_args(d_header_data, d_header_offsets, d_ids, d_origins, d_header_sigs, d_rounds, d_vote_pks,
+                         d_vote_sigs, d_vote_offsets, n, n_votes);
   const KeySetP ks = keys_now(*d);  // pinned (the queue) or current; see coa_lat_verify_device
-  a.keys = ks->ckeys.as<uint32_t>();
-  a.kflags = ks->kflags.as<uint32_t>();
-  a.ktabs = ks->ktabs.as<uint32_t>();
-  a.nk = ks->nkeys;
-  a.comb = d->comb;
-  a.wcomb = wcomb_of(*d);
-  a.kwtabs = (ks->kwide && !env_is("COA_KEY_WCOMB", "0")) ? ks->kwtabs.as<uint32_t>() : nullptr;
-  a.kw20 = ks->kw20 ? 1u : 0u;
+  key_args(a, *d, *ks);
   a.status = d_status;
   a.key_order = key_order ? 1u : 0u;
   const int lanes = cert_lanes(n + n_votes);
@@ -3036,11 +2844,7 @@ static int msg_lat_launch(int device, const CoaMsgLatIn* in, uint32_t* d_status,
   a.nh = (uint32_t)in->nh;
   a.nv = (uint32_t)in->nv;
   const KeySetP ks = keys_now(*d);  // see coa_lat_verify_device
-  a.keys = ks->ckeys.as<uint32_t>();
-  a.kflags = ks->kflags.as<uint32_t>();
-  a.ktabs = ks->ktabs.as<uint32_t>();
-  a.nk = ks->nkeys;
-  a.comb = d->comb;
+  key_args(a, *d, *ks);
   a.status = d_status;
   if (host_res) {
     a.host_res = host_res;
@@ -3075,15 +2879,8 @@ int coa_header_verify_many_device(int device, const uint8_t* d_header_data, cons
   if (!d_header_data || !d_header_offsets || !d_ids || !d_authors || !d_sigs || !d_status)
     return fail(COA_EINVAL, "null argument");
   if (check_n(n) != COA_OK) return COA_EINVAL;
-  MsgArgs a{};
-  a.hdr_data = d_header_data;
-  a.hdr_off = d_header_offsets;
-  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
-  a.authors = reinterpret_cast<const uint32_t*>(d_authors);
-  a.sigs = reinterpret_cast<const uint32_t*>(d_sigs);
-  a.n = (uint32_t)n;
-  a.status = d_status;
-  return messages_device(device, a, workspace, stream);
+  return messages_device(device, msg_args(d_header_data, d_header_offsets, d_ids, nullptr, nullptr, d_authors, d_sigs, n,
+                                          d_status), workspace, stream);
 }
 
 int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t* d_rounds, const uint8_t* d_origins,
@@ -3095,15 +2892,8 @@ int coa_vote_verify_many_device(int device, const uint8_t* d_ids, const uint64_t
   if (!d_ids || !d_rounds || !d_origins || !d_authors || !d_sigs || !d_status)
     return fail(COA_EINVAL, "null argument");
   if (check_n(n) != COA_OK) return COA_EINVAL;
-  MsgArgs a{};
-  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
-  a.rounds = d_rounds;
-  a.origins = reinterpret_cast<const uint32_t*>(d_origins);
-  a.authors = reinterpret_cast<const uint32_t*>(d_authors);
-  a.sigs = reinterpret_cast<const uint32_t*>(d_sigs);
-  a.n = (uint32_t)n;
-  a.status = d_status;
-  return messages_device(device, a, workspace, stream);
+  return messages_device(device, msg_args(nullptr, nullptr, d_ids, d_rounds, d_origins, d_authors, d_sigs, n, d_status),
+                         workspace, stream);
 }
 
 // ------------------------------------------------------------- verdicts
@@ -3137,23 +2927,13 @@ int coa_certificate_verdict_many(const uint8_t* header_data, const uint64_t* hea
   int rc = ensure_init();
   if (rc != COA_OK) return rc;
   const CertIn in{header_data, header_offsets, ids, origins, header_sigs, rounds, vote_pks, vote_sigs, vote_offsets};
-  if (!in.hdr_off || !in.ids || !in.origins || !in.hsigs || !in.rounds || !in.voff || !payload_counts || !verdicts_out)
-    return fail(COA_EINVAL, "null argument");
-  for (size_t i = 0; i < n; i++)
-    if (in.hdr_off[i + 1] < in.hdr_off[i] || in.voff[i + 1] < in.voff[i])
-      return fail(COA_EINVAL, "offsets not monotone");
-  if (in.voff[0] != 0) return fail(COA_EINVAL, "vote_offsets[0] must be 0");
-  if (in.hdr_off[n] > in.hdr_off[0] && !in.hdr_data) return fail(COA_EINVAL, "null header data");
-  if (in.voff[n] && (!in.vpks || !in.vsigs)) return fail(COA_EINVAL, "null vote arrays");
-  if (check_n(n + in.voff[n]) != COA_OK) return COA_EINVAL;
+  rc = cert_in_check(in, n, payload_counts ? verdicts_out : nullptr);
+  if (rc != COA_OK) return rc;
   if (!coa_prot_counts_fit(in.hdr_off, payload_counts, n))
     return fail(COA_EINVAL, "a payload count overruns its header");
-  std::vector<uint32_t> raw(n, 0);
+  const ProtoIn pr{payload_counts};
   rc = for_shards(
-      n,
-      [&](Dev& d, size_t lo, size_t hi) -> int {
-        return verdict_cert_shard(d, in, payload_counts, lo, hi, raw.data(), verdicts_out);
-      },
+      n, [&](Dev& d, size_t lo, size_t hi) -> int { return cert_shard(d, in, &pr, lo, hi, verdicts_out); },
       n + in.voff[n]);
   if (rc != COA_OK) return rc;
   // what stays open: every earlier check passed and the votes need the exact
