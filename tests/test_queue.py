@@ -150,8 +150,8 @@ def test_queue_small_certificate_windows_gpu(engine, monkeypatch, inline):
     """Windows of a few certificates and nothing else take the latency kernel
     with its last block writing the status words into page-locked memory,
     the arrays in the kernel arguments when they fit (C1's committee of 4:
-    ~0.6 KB a certificate), else one copy (coa_queue_hip.cpp Slot::cpub,
-    coa_certificate_verify_publish); COA_QUEUE_INLINE=0 stages them.  Windows
+    ~0.6 KB a certificate), else one copy (coa_queue_hip.cpp
+    ROUTE_CERT_PUBLISH, coa_certificate_verify_publish); COA_QUEUE_INLINE=0 stages them.  Windows
     of 1, 2 and 3 certificates with a bad vote (left open by the fused
     kernel, decided by the resolver), a bad header signature and a bad header
     id give the same bits as the host path, both ways."""
@@ -182,6 +182,47 @@ def test_queue_small_certificate_windows_gpu(engine, monkeypatch, inline):
     assert [int(g != 0) for g in got] == list(want)
     assert got[1] == engine.CERT_BAD_VOTES and got[4] == engine.CERT_BAD_HEADER_SIG and got[6] & engine.CERT_BAD_HEADER_ID
     assert m["failed_windows"] == 0
+
+
+@pytest.mark.gpu
+def test_queue_small_window_over_latency_jobs_gpu(engine):
+    """A window of certificates alone, at most 64 of them, whose jobs exceed the
+    latency kernel's 2,048: coa_certificate_verify_publish declines it and the
+    window takes the staged route.  31 certificates of a 100-key committee
+    with 67 votes each are 31 x 68 = 2,108 jobs, the fewest certificates that
+    pass the limit.  A window of 2 of them on the same queue (136 jobs, ~19.8
+    KB: more than COA_CERT_INLINE_BYTES) takes the published route by copy."""
+    import certificates as C
+
+    committee, batch = C.synth_certificates(33, committee_size=100, n_payload=4, seed=31)
+    committee.register()
+    assert all(int(batch.offsets[c + 1] - batch.offsets[c]) == 67 for c in range(33))
+    batch.vote_sigs[int(batch.offsets[7]) + 5, 40] ^= 1    # certificate 7: bad vote
+    batch.header_sigs[19, 33] ^= 1                          # certificate 19: bad header signature
+    batch.vote_sigs[int(batch.offsets[32]) + 66, 40] ^= 1  # certificate 32 (second window): bad vote
+    want = C.verify_certificate_batch(batch, committee, rng_seed=1)
+
+    def submit(q, c):
+        lo, hi = int(batch.offsets[c]), int(batch.offsets[c + 1])
+        votes = [(engine.PublicKey(bytes(batch.vote_pks[j])), engine.Signature.from_bytes(bytes(batch.vote_sigs[j])))
+                 for j in range(lo, hi)]
+        return q.submit_certificate(batch.header_inputs[c], bytes(batch.ids[c]), bytes(batch.authors[c]),
+                                    bytes(batch.header_sigs[c]), batch.round, votes)
+
+    with engine.AggregationQueue(max_batch=4096, max_delay_us=2_000_000) as q:
+        fs = [submit(q, c) for c in range(31)]
+        q.flush()
+        got = [f.result(timeout=60) for f in fs]
+        m1 = q.metrics()
+        fs = [submit(q, c) for c in (31, 32)]
+        q.flush()
+        got += [f.result(timeout=60) for f in fs]
+        m2 = q.metrics()
+    assert [int(g != 0) for g in got] == list(want)
+    assert got[7] == engine.CERT_BAD_VOTES and got[19] == engine.CERT_BAD_HEADER_SIG
+    assert got[32] == engine.CERT_BAD_VOTES and sum(g != 0 for g in got) == 3
+    assert m1["windows"] == 1 and m1["failed_windows"] == 0 and m1["deferred_requests"] >= 1
+    assert m2["windows"] == 2 and m2["failed_windows"] == 0 and m2["deferred_requests"] >= 2
 
 
 @pytest.mark.gpu

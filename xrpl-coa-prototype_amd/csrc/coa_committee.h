@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "coa_stage.h"
+
 // per-key comb of -A: 32 byte positions x 128 multiples x 24 dwords (384 KiB)
 #define COA_KEY_TAB_ENTRIES (32 * 128)
 #define COA_KEY_TAB_DWORDS (COA_KEY_TAB_ENTRIES * 24)
@@ -38,13 +40,7 @@
 #define COA_KEY_SMALL_ORDER 2u    // [8]A == O  (verify_strict rejects)
 #define COA_KEY_TORSION_FREE 4u   // [l]A == O  (batch fast path is exact)
 
-// Internal status bits of k_cert_verify (low three are the public
-// COA_CERT_BAD_* bits of include/coa_verify.h).
-#define COA_CST_BAD_HEADER_ID 1u
-#define COA_CST_BAD_HEADER_SIG 2u
-#define COA_CST_BAD_VOTES 4u
-#define COA_CST_VOTES_INCONCLUSIVE 8u  // some vote failed its own equation, or a key has torsion
-#define COA_CST_UNCACHED 16u           // author or a voter is not in the registered committee
+// (k_cert_verify's internal status bits, COA_CST_*: coa_stage.h)
 
 struct CertArgs {
   const uint8_t* hdr_data;      // Header::digest inputs, concatenated
@@ -123,31 +119,23 @@ extern "C" int coa_certificate_resolve_raw(const uint8_t* ids, const uint8_t* or
 
 // The aggregation queue's certificate windows of at most 64 certificates
 // whose jobs take the latency kernel (coa_queue_hip.cpp): the window's arrays
-// packed in page-locked h_base at the byte offsets `off` (header offsets
-// relative to off->hdr, vote offsets window-relative), device copy d_base of
-// in_bytes.  Inline in the kernel arguments when they fit
+// packed in page-locked h_base in the sections `p` (coa_qstage.h's
+// WindowPack::cert; header and vote offsets window-relative), device copy
+// d_base of in_bytes.  Inline in the kernel arguments when they fit
 // COA_CERT_INLINE_BYTES (no copy), else one H2D copy into d_base; either way
 // the kernel's last block writes (tag << 8) | status for each certificate
 // into host_res (page-locked, polled by the caller) and re-zeroes d_ctr[0..64]
 // (a device block of 65 words, zero before the first call).  Returns 1 when
 // the window is not of that size (nothing enqueued), else COA_OK or a
 // negative COA_E*.
-struct CoaCertOffsets {
-  uint64_t hdr, hoff, ids, origins, hsigs, rounds, vpks, vsigs, voff;
-};
 extern "C" int coa_certificate_verify_publish(int device, const uint8_t* h_base, uint8_t* d_base, size_t in_bytes,
-                                              const CoaCertOffsets* off, size_t n, size_t n_votes, uint32_t* d_ctr,
+                                              const CertPack* p, size_t n, size_t n_votes, uint32_t* d_ctr,
                                               uint32_t* host_res, uint32_t tag, void* stream);
 
 // Host copies spread over the runtime's copy threads (COA_PACK_THREADS):
 // the aggregation queue packs large windows into page-locked staging with
 // it.  Returns when every segment is copied.
-struct CoaCopySeg {
-  void* dst;
-  const void* src;
-  size_t bytes;
-};
-extern "C" void coa_copy_segments(const CoaCopySeg* segs, size_t n);
+extern "C" void coa_copy_segments(const Seg* segs, size_t n);
 
 hipError_t coa_launch_key_flags(const uint32_t* keys, uint32_t nk, uint32_t* flags, hipStream_t s);
 hipError_t coa_launch_key_tables(const uint32_t* keys, uint32_t nk, uint32_t* tabs, hipStream_t s);
@@ -162,10 +150,12 @@ hipError_t coa_launch_key_wcombs20(const uint32_t* tabs, uint32_t nk, uint32_t* 
 size_t coa_cert_scratch_bytes(uint64_t jobs, bool key_order);
 
 // coa_certificate_verify_many_device with the job order chosen by the caller:
-// key_order 1 (the public device-resident round) sorts a call of >= 16,384
-// jobs by committee key, 0 keeps certificate order (the aggregation queue's
-// windows: concurrent windows lost more to the sort's launches than the order
-// gained, profiles/r05_cert_keysort_ab.txt).  The workspace must hold
+// key_order 1 (the public device-resident round, and the aggregation queue's
+// windows unless COA_QUEUE_KEYSORT=0: profiles/r06_keysort_ab.txt) sorts a
+// call of >= 16,384 jobs by committee key, 0 keeps certificate order (the
+// queue's windows up to round 5, whose concurrent windows lost more to the
+// sort's launches than the order gained, profiles/r05_cert_keysort_ab.txt).
+// The workspace must hold
 // coa_cert_scratch_bytes(n + n_votes, key_order) bytes.
 extern "C" int coa_certificate_verify_many_device_order(
     int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets, const uint8_t* d_ids,

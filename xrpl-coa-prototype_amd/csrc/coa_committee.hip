@@ -1120,8 +1120,8 @@ static size_t cert_slab_bytes(uint64_t jobs, uint64_t lanes) {
 // ... | key-order sort, only for a call that may sort (key_order and at
 // least COA_SORT_MIN_JOBS jobs): bin totals / cursors [COA_SORT_BINS], counts
 // [COA_SORT_WGS][COA_SORT_BINS], each job's bin [jobs], the permutation [jobs]
-// (~4.2 MB + 8 B per job; a latency, pipelined-chunk or queue workspace does
-// not carry it)
+// (~4.2 MB + 8 B per job; a latency or pipelined-chunk workspace does not
+// carry it)
 size_t coa_cert_scratch_bytes(uint64_t jobs, bool key_order) {
   const uint64_t lanes = cert_tp_lanes(jobs ? jobs : 1);
   const size_t base = 256 + cert_slab_bytes(jobs, lanes) + (size_t)(jobs ? jobs : 1) * 32;
@@ -1156,9 +1156,11 @@ hipError_t coa_launch_cert_verify(CertArgs a, int lanes_per_sig, uint32_t* pscr,
   // jobs in key order when the caller asks for it, the committee fits the
   // bins and the call is large enough to pay for the sort
   // (COA_CERT_KEYSORT=0: certificate order everywhere, A/B).  The callers
-  // that ask: the device-resident round (+16-18 %); not the pipelined host
-  // chunks nor the queue's windows, whose concurrent launches lost more to
-  // the sort's own launches than the order gained (profiles/r05_cert_keysort_ab.txt)
+  // that ask: the device-resident round (+16-18 %) and, since round 6, the
+  // queue's windows (COA_QUEUE_KEYSORT, within noise either way:
+  // profiles/r06_keysort_ab.txt); not the pipelined host chunks, whose
+  // concurrent launches lost more to the sort's own launches than the order
+  // gained (profiles/r05_cert_keysort_ab.txt)
   const char* ks = getenv("COA_CERT_KEYSORT");
   if (a.key_order && a.nk > 0 && a.nk + 1 <= COA_SORT_BINS && jobs >= COA_SORT_MIN_JOBS &&
       !(ks && ks[0] == '0' && ks[1] == 0)) {

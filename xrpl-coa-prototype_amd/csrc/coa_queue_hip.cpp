@@ -16,15 +16,21 @@
 // does): "cumask" (the default) -- hipExtStreamCreateWithCUMask with every
 // CU enabled: HIP never shares a CU-masked stream's queue, whatever
 // GPU_MAX_HW_QUEUES says; "priority" -- the high-priority pool (its own 4
-// queues) for the verify lane; "plain" -- shared queues (the round-3 form).  launch() packs the
-// launch's parts (one per intake shard) straight into one pinned block --
-// the parts are never merged first -- issues ONE host-to-device copy, the
-// engine's device-resident entry points (asynchronous with an explicit
-// workspace, no engine lock) and ONE device-to-host copy on the slot's
-// stream, records an event and returns; complete() waits for the event and
-// scatters the outputs back to the parts.  So while window N runs on slot A,
-// window N + 1 is packed and enqueued on slot B, and the copies of one window
-// overlap the kernels of the other.
+// queues) for the verify lane; "plain" -- shared queues (the round-3 form).
+//
+// What a window's blocks hold is coa_qstage.h's (host code only, tested on
+// the CPU): the layout of the input and output blocks, the packer, the
+// scatter and the resolver's gather / write-back.  This file holds the HIP
+// around it.  enqueue() lays the launch out, packs its parts (one per intake
+// shard) straight into the slot's pinned input block -- the parts are never
+// merged first -- and picks a route (coa_q::Route), each a member function:
+// staged -- ONE host-to-device copy, the engine's device-resident entry points
+// (asynchronous with an explicit workspace, no engine lock) and ONE
+// device-to-host copy on the slot's stream, then an event that complete()
+// waits for -- or, for a small window of one kind, one of the publish routes.
+// complete() then scatters the outputs back to the parts.  So while window N
+// runs on slot A, window N + 1 is packed and enqueued on slot B, and the
+// copies of one window overlap the kernels of the other.
 //
 // Per kind:
 //   signatures    coa_ed25519_verify_strict_many_device (Signature::verify);
@@ -43,7 +49,7 @@
 //   headers, votes  the committee-comb message kernels, Header::digest checked
 //                 and Vote::digest hashed on the device: alone in a window of
 //                 at most 64 messages, the latency kernel in publish mode
-//                 (Slot::mpub); a window of at most COA_QUEUE_MSG_LAT_MAX
+//                 (ROUTE_MSG_PUBLISH); a window of at most COA_QUEUE_MSG_LAT_MAX
 //                 messages, the latency kernel with its status words staged
 //                 (coa_msg_lat_verify_device); a larger one,
 //                 coa_header_verify_many_device / coa_vote_verify_many_device.
@@ -59,8 +65,9 @@
 // regrown on demand) and freed; the queue then re-runs the window through
 // retry() on the recovery context of another device (one per device, used
 // only by retries).  COA_QUEUE_FAULT=<k> makes every k-th window's launch
-// fail after its input copy is enqueued (fault injection for the recovery
-// tests; never set in production).
+// fail once its input copy is enqueued -- before anything is, on the routes
+// without a copy of their own (fault injection for the recovery tests; never
+// set in production).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,6 +82,7 @@
 
 #include "coa_committee.h"
 #include "coa_latency.h"
+#include "coa_qstage.h"
 #include "coa_queue.h"
 
 #define COA_QUEUE_SLOTS_DEFAULT 4
@@ -83,7 +91,6 @@
 // nothing and shorten the wait for a slot: at C4's 1,000 batches/s, 8 slots
 // give p50 16.0 ms against 19.6 with 4 (profiles/r05_digest_slots_ab.jsonl)
 #define COA_QUEUE_DIGEST_SLOTS_DEFAULT 8
-#define COA_LAT_RES_WORDS 64  // result words of an inline latency or published certificate / message window
 // Largest message window (headers + votes) the latency kernel takes
 // (COA_QUEUE_MSG_LAT_MAX, read at queue creation): the largest window size of
 // tools/queue_message_ab.py's device-side sweep at which k_msg_verify_lat was
@@ -93,7 +100,6 @@
 
 namespace {
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int64_t ns_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
   return std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
 }
@@ -120,24 +126,15 @@ struct Slot {
   bool launched = false;  // device work was enqueued (complete() must drain it)
   void* keys = nullptr;   // the key-cache generation the launch pinned (coa_keycache_pin)
   bool lat = false;       // the launch's signatures took the latency kernel (result words)
-  // a window of at most COA_LAT_INLINE signatures and nothing else: records in
-  // the kernel arguments, verdict words straight into lres (page-locked,
-  // coherent), which complete() polls for ltag -- no copies, no event wait
-  bool inl = false;
-  uint32_t* lres = nullptr;  // COA_LAT_RES_WORDS words
+  coa_q::WindowPack pack;  // the launch's staging layout
+  // How the launch's results come back (coa_qstage.h).  On a publish route the
+  // kernel writes npub result words tagged ltag straight into lres (page-locked,
+  // coherent), which complete() polls -- no D2H copy, no event wait.
+  coa_q::Route route = coa_q::ROUTE_STAGED;
+  uint32_t* lres = nullptr;  // COA_PUBLISH_WORDS words
   uint32_t ltag = 0;
-  // a window of at most 64 certificates and nothing else, on the latency
-  // kernel: its last block writes the status words into lres (no status
-  // memset, no D2H copy, no event wait; inline arguments when the window
-  // fits, coa_certificate_verify_publish); dctr is its device counter block
-  bool cpub = false;
-  uint32_t* dctr = nullptr;  // 65 device words, zero between launches
-  // a window of at most COA_LAT_RES_WORDS headers and votes and nothing else
-  // the device runs: one H2D copy, the message latency kernel, its last block
-  // publishing the status words into lres (coa_msg_lat_verify_publish)
-  bool mpub = false;
-  // output offsets of the current launch
-  size_t o_v = 0, o_c = 0, o_d = 0, o_m = 0;
+  size_t npub = 0;           // result words the launch publishes (new_tag)
+  uint32_t* dctr = nullptr;  // the publishing kernels' 65 device counter words, zero between launches
 };
 
 // A slot's staging grows geometrically (twice what a window needs) and an
@@ -366,7 +363,7 @@ class HipBackend : public coa_q::Backend {
   // (allocated once; null when the allocation failed: such windows then take
   // the staged path)
   static uint32_t* lat_words(Slot& sl) {
-    if (!sl.lres && hipHostMalloc(reinterpret_cast<void**>(&sl.lres), COA_LAT_RES_WORDS * sizeof(uint32_t),
+    if (!sl.lres && hipHostMalloc(reinterpret_cast<void**>(&sl.lres), COA_PUBLISH_WORDS * sizeof(uint32_t),
                                   hipHostMallocCoherent) != hipSuccess) {
       sl.lres = nullptr;
       (void)hipGetLastError();
@@ -524,10 +521,19 @@ class HipBackend : public coa_q::Backend {
     return true;
   }
 
-  // Input block: verify msgs | pks | sigs, certificate arrays, digest data |
-  // offsets (256-byte aligned sections), each section the parts' arrays one
-  // after another (offsets rebased).  Output block: verdicts | status words |
-  // 64-byte digests.
+  // The next tag of the slot's result words, the launch's n of them cleared
+  // (no tag matches 0).
+  static void new_tag(Slot& sl, size_t n) {
+    std::memset(sl.lres, 0, n * sizeof(uint32_t));
+    sl.ltag = (sl.ltag + 1) & 0xffffffu;
+    if (sl.ltag == 0) sl.ltag = 1;
+    sl.npub = n;
+  }
+
+  // Layout, pack, route (coa_qstage.h): the launch's parts packed into the
+  // slot's page-locked input block, then one of the publish routes
+  // (Slot::route) when the window is small and of one kind, else the staged
+  // route.
   int enqueue(Slot& sl, coa_q::Launch& L, bool inject) {
     if (hipSetDevice(sl.dev) != hipSuccess) return COA_EHIP;
     const auto t_pack = std::chrono::steady_clock::now();
@@ -536,282 +542,225 @@ class HipBackend : public coa_q::Backend {
     // one-lane throughput kernels); its inputs are interleaved 128-byte
     // records and its results 32-bit words
     sl.lat = L.nv > 0 && L.nv <= coa_lat_max();
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-      const size_t at = o;
-      o = al256(o + bytes);
-      return at;
-    };
-    const size_t i_vm = take(L.nv * (sl.lat ? 128 : 32)), i_vp = take(sl.lat ? 0 : L.nv * 32),
-                 i_vs = take(sl.lat ? 0 : L.nv * 64);
-    const size_t i_ch = take(L.hbytes + 16), i_cho = take((L.nc + 1) * 8), i_cid = take(L.nc * 32),
-                 i_cor = take(L.nc * 32), i_chs = take(L.nc * 64), i_crd = take(L.nc * 8),
-                 i_cvp = take(L.nvotes * 32), i_cvs = take(L.nvotes * 64), i_cvo = take((L.nc + 1) * 8);
-    const size_t i_dd = take(L.dbytes + 16), i_do = take((L.nd + 1) * 8);
+    sl.pack = coa_q::window_layout(L, sl.lat);
+    sl.route = coa_q::ROUTE_STAGED;
+    const coa_q::WindowPack& p = sl.pack;
     const size_t msgs = L.nhd + L.nvt;
-    const size_t i_hd = take(L.nhd ? L.hdbytes + 16 : 0), i_hdo = take(L.nhd ? (L.nhd + 1) * 8 : 0),
-                 i_hid = take(L.nhd * 32), i_hau = take(L.nhd * 32), i_hsg = take(L.nhd * 64);
-    const size_t i_tid = take(L.nvt * 32), i_trd = take(L.nvt * 8), i_tor = take(L.nvt * 32),
-                 i_tau = take(L.nvt * 32), i_tsg = take(L.nvt * 64);
-    const size_t in_bytes = o;
-    o = 0;
-    sl.o_v = take(sl.lat ? L.nv * 4 : L.nv);
-    sl.o_c = take(L.nc * 4);
-    sl.o_d = take(L.nd * 64);
-    sl.o_m = take(msgs * 4);  // the headers' status words, then the votes'
-    const size_t out_bytes = o;
     const bool msg_lat = msgs > 0 && msgs <= msg_lat_max_;
     const size_t ws_m = (msgs && !msg_lat) ? coa_message_workspace_bytes(std::max(L.nhd, L.nvt)) : 0;
     const size_t ws_v = L.nv ? coa_verify_workspace_bytes(L.nv) : 0;
     const size_t ws_c = L.nc ? coa_cert_scratch_bytes(L.nc + L.nvotes, keysort_) : 0;
     const size_t caps0 = sl.cap_hin + sl.cap_hout + sl.cap_din + sl.cap_dout + sl.cap_ws;
-    if (grow_pinned(sl.hin, sl.cap_hin, in_bytes, sl.grave) != hipSuccess ||
-        grow_pinned(sl.hout, sl.cap_hout, out_bytes, sl.grave) != hipSuccess ||
-        grow_dev(sl.din, sl.cap_din, in_bytes, sl.grave) != hipSuccess ||
-        grow_dev(sl.dout, sl.cap_dout, out_bytes, sl.grave) != hipSuccess ||
+    if (grow_pinned(sl.hin, sl.cap_hin, p.in_total, sl.grave) != hipSuccess ||
+        grow_pinned(sl.hout, sl.cap_hout, p.out_total, sl.grave) != hipSuccess ||
+        grow_dev(sl.din, sl.cap_din, p.in_total, sl.grave) != hipSuccess ||
+        grow_dev(sl.dout, sl.cap_dout, p.out_total, sl.grave) != hipSuccess ||
         grow_dev(sl.ws, sl.cap_ws, std::max(std::max(ws_v, ws_c), ws_m) + 256, sl.grave) != hipSuccess)
       return COA_ENOMEM;
     if (sl.cap_hin + sl.cap_hout + sl.cap_din + sl.cap_dout + sl.cap_ws != caps0) grows_++;
-    uint8_t* h = static_cast<uint8_t*>(sl.hin);
     // the bulk copies of a large window go to the runtime's copy threads (a
     // C3 round is ~68 MB: one thread's memcpy would be slower than PCIe)
-    std::vector<CoaCopySeg> bulk;
-    auto copy = [&bulk](void* dst, const void* src, size_t bytes) {
-      if (bytes) bulk.push_back({dst, src, bytes});
-    };
-    size_t v = 0, c = 0, cv = 0, hb = 0, dn = 0, db = 0, mh = 0, mhb = 0, mt = 0;
-    uint64_t* hdo = reinterpret_cast<uint64_t*>(h + i_hdo);
-    if (L.nhd) hdo[0] = 0;
-    uint64_t* cho = reinterpret_cast<uint64_t*>(h + i_cho);
-    uint64_t* cvo = reinterpret_cast<uint64_t*>(h + i_cvo);
-    uint64_t* dof = reinterpret_cast<uint64_t*>(h + i_do);
-    cho[0] = cvo[0] = dof[0] = 0;
-    for (const coa_q::Window* w : L.parts) {
-      if (w->nv && sl.lat) {  // i_vm .. : [nv][msg | pk | R | s]
-        for (size_t i = 0; i < w->nv; i++) {
-          uint8_t* r = h + i_vm + (v + i) * 128;
-          std::memcpy(r, w->v_msgs.data() + i * 32, 32);
-          std::memcpy(r + 32, w->v_pks.data() + i * 32, 32);
-          std::memcpy(r + 64, w->v_sigs.data() + i * 64, 64);
-        }
-        v += w->nv;
-      } else if (w->nv) {
-        copy(h + i_vm + v * 32, w->v_msgs.data(), w->nv * 32);
-        copy(h + i_vp + v * 32, w->v_pks.data(), w->nv * 32);
-        copy(h + i_vs + v * 64, w->v_sigs.data(), w->nv * 64);
-        v += w->nv;
-      }
-      // certificates from their refs (the window's own bytes, or a borrowed
-      // request's arrays): the small fixed fields here, the header input and
-      // the votes (~9.7 KB of a C3 certificate's 9.9) as bulk segments
-      for (size_t i = 0; i < w->nc; i++, c++) {
-        const coa_q::Window::CertRef& r = w->c_refs[i];
-        copy(h + i_ch + hb, r.hdr, r.hlen);
-        hb += r.hlen;
-        cho[c + 1] = hb;
-        std::memcpy(h + i_cid + c * 32, r.id, 32);
-        std::memcpy(h + i_cor + c * 32, r.origin, 32);
-        std::memcpy(h + i_chs + c * 64, r.hsig, 64);
-        std::memcpy(h + i_crd + c * 8, &r.round, 8);
-        copy(h + i_cvp + cv * 32, r.vpks, r.nv * 32);
-        copy(h + i_cvs + cv * 64, r.vsigs, r.nv * 64);
-        cv += r.nv;
-        cvo[c + 1] = cv;
-      }
-      if (w->nd) {
-        copy(h + i_dd + db, w->d_data.data(), w->d_data.size());
-        for (size_t i = 1; i <= w->nd; i++) dof[dn + i] = db + w->d_offs[i];
-        dn += w->nd;
-        db += w->d_data.size();
-      }
-      if (w->nhd) {
-        copy(h + i_hd + mhb, w->hd_data.data(), w->hd_data.size());
-        for (size_t i = 1; i <= w->nhd; i++) hdo[mh + i] = mhb + w->hd_offs[i];
-        copy(h + i_hid + mh * 32, w->hd_ids.data(), w->nhd * 32);
-        copy(h + i_hau + mh * 32, w->hd_authors.data(), w->nhd * 32);
-        copy(h + i_hsg + mh * 64, w->hd_sigs.data(), w->nhd * 64);
-        mh += w->nhd;
-        mhb += w->hd_data.size();
-      }
-      if (w->nvt) {
-        copy(h + i_tid + mt * 32, w->vt_ids.data(), w->nvt * 32);
-        copy(h + i_trd + mt * 8, w->vt_rounds.data(), w->nvt * 8);
-        copy(h + i_tor + mt * 32, w->vt_origins.data(), w->nvt * 32);
-        copy(h + i_tau + mt * 32, w->vt_authors.data(), w->nvt * 32);
-        copy(h + i_tsg + mt * 64, w->vt_sigs.data(), w->nvt * 64);
-        mt += w->nvt;
-      }
-    }
+    std::vector<Seg> bulk;
+    coa_q::window_pack(static_cast<uint8_t*>(sl.hin), p, L, bulk);
     size_t bulk_bytes = 0;
-    for (const CoaCopySeg& g : bulk) bulk_bytes += g.bytes;
+    for (const Seg& g : bulk) bulk_bytes += g.bytes;
     if (bulk_bytes >= (1u << 20)) {
       coa_copy_segments(bulk.data(), bulk.size());
     } else {
-      for (const CoaCopySeg& g : bulk) std::memcpy(g.dst, g.src, g.bytes);
+      for (const Seg& g : bulk) std::memcpy(g.dst, g.src, g.bytes);
     }
     const auto t_enq = std::chrono::steady_clock::now();
     L.stage_ns[COA_QSTAGE_PACK] += ns_between(t_pack, t_enq);
     if (L.nv + L.nc + L.nd + msgs == 0) return COA_OK;  // bare vote batches only: left to resolve()
-    struct EnqClock {  // ENQUEUE stage: every return below
-      coa_q::Launch& L;
-      std::chrono::steady_clock::time_point t;
-      ~EnqClock() { L.stage_ns[COA_QSTAGE_ENQUEUE] += ns_between(t, std::chrono::steady_clock::now()); }
-    } enq_clock{L, t_enq};
-    // the ENQUEUE stage's parts (Launch::enq_ns): each mark() charges the time
-    // since the previous one to part k
-    auto t_mark = t_enq;
-    auto mark = [&](int k) {
+    EnqClock clk{L, t_enq, t_enq};
+    const bool alone_v = L.nc == 0 && L.nd == 0 && msgs == 0, alone_c = L.nv == 0 && L.nd == 0 && msgs == 0,
+               alone_m = L.nv == 0 && L.nc == 0 && L.nd == 0;
+    if (inline_ok_ && sl.lat && L.nv <= COA_LAT_INLINE && alone_v && lat_words(sl) != nullptr) {
+      sl.route = coa_q::ROUTE_SIG_INLINE;
+      return enqueue_sig_inline(sl, L, inject, clk);
+    }
+    if (inline_ok_ && L.nc > 0 && L.nc <= COA_PUBLISH_WORDS && alone_c && lat_words(sl) != nullptr &&
+        ctr_words(sl) != nullptr) {
+      sl.route = coa_q::ROUTE_CERT_PUBLISH;
+      const int rc = enqueue_cert_publish(sl, L, inject, clk);
+      if (rc != 1) return rc;
+      sl.route = coa_q::ROUTE_STAGED;  // too many jobs for the latency kernel
+    }
+    if (msgs) L.msg_route = msg_lat ? coa_q::Launch::MSG_LATENCY : coa_q::Launch::MSG_THROUGHPUT;
+    if (inline_ok_ && msg_lat && msgs <= COA_PUBLISH_WORDS && alone_m && lat_words(sl) != nullptr &&
+        ctr_words(sl) != nullptr) {
+      sl.route = coa_q::ROUTE_MSG_PUBLISH;
+      return enqueue_msg_publish(sl, L, inject, clk);
+    }
+    return enqueue_staged(sl, L, msg_lat, inject, clk);
+  }
+
+  // The ENQUEUE stage of a launch: all of enqueue() after the pack, whichever
+  // way it returns, and its parts (Launch::enq_ns) -- each mark() charges the
+  // time since the previous one to part k.
+  struct EnqClock {
+    coa_q::Launch& L;
+    const std::chrono::steady_clock::time_point t0;
+    std::chrono::steady_clock::time_point t_mark;
+    ~EnqClock() { L.stage_ns[COA_QSTAGE_ENQUEUE] += ns_between(t0, std::chrono::steady_clock::now()); }
+    void mark(int k) {
       const auto t = std::chrono::steady_clock::now();
       L.enq_ns[k] += ns_between(t_mark, t);
       t_mark = t;
-    };
-    sl.cpub = sl.mpub = false;
-    sl.inl = inline_ok_ && sl.lat && L.nv <= COA_LAT_INLINE && L.nc == 0 && L.nd == 0 && msgs == 0 &&
-             lat_words(sl) != nullptr;
-    if (sl.inl) {
-      // a few signatures alone (Header::verify / Vote::verify at low load):
-      // the packed records go in the kernel arguments and the verdict words
-      // come back by the kernel's own stores, as coa_ed25519_verify_strict
-      // does -- the staged path's two copies (and the event wait) were most
-      // of such a window's time besides the kernel
-      std::memset(sl.lres, 0, L.nv * sizeof(uint32_t));  // no tag matches 0
-      sl.ltag = (sl.ltag + 1) & 0xffffffu;
-      if (sl.ltag == 0) sl.ltag = 1;
-      sl.launched = true;
-      if (inject) return COA_EHIP;  // fault injection: nothing launched
-      if (!sl.keys) sl.keys = coa_keycache_pin(sl.dev);
-      coa_keycache_use(sl.keys);
-      mark(coa_q::Launch::ENQ_PIN);
-      const int rc = coa_lat_verify_inline(sl.dev, h + i_vm, L.nv, sl.lres, sl.ltag, sl.s);
-      coa_keycache_use(nullptr);
-      mark(coa_q::Launch::ENQ_LAUNCH);
-      if (rc != COA_OK) return rc;
-      const hipError_t er = hipEventRecord(sl.ev, sl.s);
-      mark(coa_q::Launch::ENQ_EVENT);
-      return er == hipSuccess ? COA_OK : COA_EHIP;
     }
-    sl.cpub = inline_ok_ && L.nc > 0 && L.nc <= COA_LAT_RES_WORDS && L.nv == 0 && L.nd == 0 && msgs == 0 &&
-              lat_words(sl) != nullptr && ctr_words(sl) != nullptr;
-    if (sl.cpub) {
-      // certificates alone, few (Certificate::verify at low load): see Slot::cpub
-      if (inject) {
-        sl.launched = true;
-        return COA_EHIP;  // fault injection: nothing launched
-      }
-      std::memset(sl.lres, 0, L.nc * sizeof(uint32_t));
-      sl.ltag = (sl.ltag + 1) & 0xffffffu;
-      if (sl.ltag == 0) sl.ltag = 1;
-      if (!sl.keys) sl.keys = coa_keycache_pin(sl.dev);
+  };
+
+  // The committee key-cache generation a route's launches read, for its
+  // scope: the one the slot has pinned, the current one pinned first when it
+  // holds none (finish() un-pins it -- a registration meanwhile builds the
+  // next generation beside it).
+  struct KeyUse {
+    explicit KeyUse(Slot& sl, bool pin = true) {
+      if (pin && !sl.keys) sl.keys = coa_keycache_pin(sl.dev);
       coa_keycache_use(sl.keys);
-      mark(coa_q::Launch::ENQ_PIN);
-      const CoaCertOffsets off{i_ch, i_cho, i_cid, i_cor, i_chs, i_crd, i_cvp, i_cvs, i_cvo};
-      const int rc = coa_certificate_verify_publish(sl.dev, h, static_cast<uint8_t*>(sl.din), in_bytes, &off, L.nc,
-                                                    L.nvotes, sl.dctr, sl.lres, sl.ltag, sl.s);
-      coa_keycache_use(nullptr);
-      mark(coa_q::Launch::ENQ_LAUNCH);  // (its H2D copy, when the window does not fit the arguments, included)
-      if (rc == COA_OK) {
-        sl.launched = true;
-        const hipError_t er = hipEventRecord(sl.ev, sl.s);
-        mark(coa_q::Launch::ENQ_EVENT);
-        return er == hipSuccess ? COA_OK : COA_EHIP;
-      }
-      if (rc != 1) {
-        sl.launched = true;  // something may be enqueued: finish() drains the stream
-        return rc;
-      }
-      sl.cpub = false;  // too many jobs for the latency kernel: the staged path below
     }
-    uint8_t* d = static_cast<uint8_t*>(sl.din);
-    uint8_t* dout = static_cast<uint8_t*>(sl.dout);
-    // the window's messages as the device entries take them
-    CoaMsgLatIn msg_in{};
+    ~KeyUse() { coa_keycache_use(nullptr); }
+  };
+
+  // One H2D copy of the whole input block.
+  static int copy_in(Slot& sl, EnqClock& clk) {
+    if (hipMemcpyAsync(sl.din, sl.hin, sl.pack.in_total, hipMemcpyHostToDevice, sl.s) != hipSuccess) return COA_EHIP;
+    clk.mark(coa_q::Launch::ENQ_H2D);
+    sl.launched = true;
+    return COA_OK;
+  }
+  // The event finish() waits for, or queries while it polls.
+  static int record(Slot& sl, EnqClock& clk) {
+    const hipError_t e = hipEventRecord(sl.ev, sl.s);
+    clk.mark(coa_q::Launch::ENQ_EVENT);
+    return e == hipSuccess ? COA_OK : COA_EHIP;
+  }
+
+  // The window's headers and votes in block d, as the latency entries take them.
+  static CoaMsgLatIn msg_lat_in(const uint8_t* d, const coa_q::WindowPack& p, const coa_q::Launch& L) {
+    const MsgIn h = msg_view(d, p.hdr, false), v = msg_view(d, p.vote, true);
+    CoaMsgLatIn in{};
     if (L.nhd) {
-      msg_in.hdr_data = d + i_hd;
-      msg_in.hdr_off = reinterpret_cast<const uint64_t*>(d + i_hdo);
-      msg_in.hids = d + i_hid;
-      msg_in.hauthors = d + i_hau;
-      msg_in.hsigs = d + i_hsg;
-      msg_in.nh = L.nhd;
+      in.hdr_data = h.hdr_data, in.hdr_off = h.hdr_off;
+      in.hids = h.ids, in.hauthors = h.authors, in.hsigs = h.sigs, in.nh = L.nhd;
     }
     if (L.nvt) {
-      msg_in.vids = d + i_tid;
-      msg_in.vrounds = reinterpret_cast<const uint64_t*>(d + i_trd);
-      msg_in.vorigins = d + i_tor;
-      msg_in.vauthors = d + i_tau;
-      msg_in.vsigs = d + i_tsg;
-      msg_in.nv = L.nvt;
+      in.vids = v.ids, in.vrounds = v.rounds, in.vorigins = v.origins;
+      in.vauthors = v.authors, in.vsigs = v.sigs, in.nv = L.nvt;
     }
-    if (msgs) L.msg_route = msg_lat ? coa_q::Launch::MSG_LATENCY : coa_q::Launch::MSG_THROUGHPUT;
-    sl.mpub = inline_ok_ && msg_lat && msgs <= COA_LAT_RES_WORDS && L.nv == 0 && L.nc == 0 && L.nd == 0 &&
-              lat_words(sl) != nullptr && ctr_words(sl) != nullptr;
-    if (sl.mpub) {
-      // headers and votes alone, few (Header::verify / Vote::verify at low
-      // load): see Slot::mpub.  No status memset, no D2H copy, no event wait
-      std::memset(sl.lres, 0, msgs * sizeof(uint32_t));  // no tag matches 0
-      sl.ltag = (sl.ltag + 1) & 0xffffffu;
-      if (sl.ltag == 0) sl.ltag = 1;
-      if (hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, sl.s) != hipSuccess) return COA_EHIP;
-      mark(coa_q::Launch::ENQ_H2D);
-      sl.launched = true;
-      if (inject) return COA_EHIP;  // fault injection: the copy is in flight, the kernel never runs
-      if (!sl.keys) sl.keys = coa_keycache_pin(sl.dev);
-      coa_keycache_use(sl.keys);
-      mark(coa_q::Launch::ENQ_PIN);
-      const int rc = coa_msg_lat_verify_publish(sl.dev, &msg_in, sl.dctr, sl.lres, sl.ltag, sl.s);
-      coa_keycache_use(nullptr);
-      mark(coa_q::Launch::ENQ_LAUNCH);
-      if (rc != COA_OK) return rc;
-      const hipError_t er = hipEventRecord(sl.ev, sl.s);
-      mark(coa_q::Launch::ENQ_EVENT);
-      return er == hipSuccess ? COA_OK : COA_EHIP;
-    }
-    if (hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, sl.s) != hipSuccess) return COA_EHIP;
-    mark(coa_q::Launch::ENQ_H2D);
+    return in;
+  }
+
+  // A few signatures alone (Header::verify / Vote::verify at low load): the
+  // packed records go in the kernel arguments and the verdict words come back
+  // by the kernel's own stores, as coa_ed25519_verify_strict does -- the
+  // staged route's two copies (and the event wait) were most of such a
+  // window's time besides the kernel.
+  static int enqueue_sig_inline(Slot& sl, coa_q::Launch& L, bool inject, EnqClock& clk) {
+    new_tag(sl, L.nv);
     sl.launched = true;
+    if (inject) return COA_EHIP;  // fault injection: nothing launched
+    int rc;
+    {
+      KeyUse keys(sl);
+      clk.mark(coa_q::Launch::ENQ_PIN);
+      rc = coa_lat_verify_inline(sl.dev, static_cast<const uint8_t*>(sl.hin) + sl.pack.v_recs.at, L.nv, sl.lres,
+                                 sl.ltag, sl.s);
+    }
+    clk.mark(coa_q::Launch::ENQ_LAUNCH);
+    return rc == COA_OK ? record(sl, clk) : rc;
+  }
+
+  // Certificates alone, few (Certificate::verify at low load).  Returns 1,
+  // with nothing enqueued, when their jobs exceed the latency kernel's: the
+  // window then takes the staged route.
+  static int enqueue_cert_publish(Slot& sl, coa_q::Launch& L, bool inject, EnqClock& clk) {
+    if (inject) {
+      sl.launched = true;
+      return COA_EHIP;  // fault injection: nothing launched
+    }
+    new_tag(sl, L.nc);
+    int rc;
+    {
+      KeyUse keys(sl);
+      clk.mark(coa_q::Launch::ENQ_PIN);
+      rc = coa_certificate_verify_publish(sl.dev, static_cast<const uint8_t*>(sl.hin), static_cast<uint8_t*>(sl.din),
+                                          sl.pack.in_total, &sl.pack.cert, L.nc, L.nvotes, sl.dctr, sl.lres, sl.ltag,
+                                          sl.s);
+    }
+    clk.mark(coa_q::Launch::ENQ_LAUNCH);  // (its H2D copy, when the window does not fit the arguments, included)
+    if (rc == 1) return 1;
+    sl.launched = true;  // on a failure something may be enqueued: finish() drains the stream
+    return rc == COA_OK ? record(sl, clk) : rc;
+  }
+
+  // Headers and votes alone, few (Header::verify / Vote::verify at low load).
+  // No status memset, no D2H copy, no event wait.
+  static int enqueue_msg_publish(Slot& sl, coa_q::Launch& L, bool inject, EnqClock& clk) {
+    new_tag(sl, L.nhd + L.nvt);
+    if (copy_in(sl, clk) != COA_OK) return COA_EHIP;
+    if (inject) return COA_EHIP;  // fault injection: the copy is in flight, the kernel never runs
+    const CoaMsgLatIn in = msg_lat_in(static_cast<const uint8_t*>(sl.din), sl.pack, L);
+    int rc;
+    {
+      KeyUse keys(sl);
+      clk.mark(coa_q::Launch::ENQ_PIN);
+      rc = coa_msg_lat_verify_publish(sl.dev, &in, sl.dctr, sl.lres, sl.ltag, sl.s);
+    }
+    clk.mark(coa_q::Launch::ENQ_LAUNCH);
+    return rc == COA_OK ? record(sl, clk) : rc;
+  }
+
+  // Everything else: ONE H2D copy, the device-resident entry of each kind the
+  // window holds, ONE D2H copy of the output block.
+  int enqueue_staged(Slot& sl, coa_q::Launch& L, bool msg_lat, bool inject, EnqClock& clk) {
+    if (copy_in(sl, clk) != COA_OK) return COA_EHIP;
     if (inject) return COA_EHIP;  // fault injection: the copy is in flight, the kernels never run
+    const coa_q::WindowPack& p = sl.pack;
+    const uint8_t* d = static_cast<const uint8_t*>(sl.din);
+    uint8_t* dout = static_cast<uint8_t*>(sl.dout);
+    auto out_words = [dout](const Sec& s) { return reinterpret_cast<uint32_t*>(dout + s.at); };
+    const size_t msgs = L.nhd + L.nvt;
     int rc = COA_OK;
-    // both read the committee key cache: the launch pins the current
-    // generation until complete() (a registration meanwhile builds the next
-    // one beside it) and its launches read that one
-    if ((sl.lat || L.nc || msgs) && !sl.keys) sl.keys = coa_keycache_pin(sl.dev);
-    coa_keycache_use(sl.keys);
-    mark(coa_q::Launch::ENQ_PIN);
-    if (L.nv && sl.lat)
-      rc = coa_lat_verify_device(sl.dev, d + i_vm, L.nv, reinterpret_cast<uint32_t*>(dout + sl.o_v), sl.s);
-    else if (L.nv)
-      rc = coa_ed25519_verify_strict_many_device(sl.dev, d + i_vm, 32, d + i_vp, d + i_vs, L.nv, dout + sl.o_v, sl.ws,
-                                                 sl.s);
-    if (rc == COA_OK && L.nc) {
-      // key order for a large window (COA_QUEUE_KEYSORT): see
-      // coa_certificate_verify_many_device_order
-      rc = coa_certificate_verify_many_device_order(
-          sl.dev, d + i_ch, reinterpret_cast<const uint64_t*>(d + i_cho), d + i_cid, d + i_cor, d + i_chs,
-          reinterpret_cast<const uint64_t*>(d + i_crd), d + i_cvp, d + i_cvs,
-          reinterpret_cast<const uint64_t*>(d + i_cvo), L.nc, L.nvotes, reinterpret_cast<uint32_t*>(dout + sl.o_c),
-          sl.ws, sl.s, keysort_ ? 1 : 0);
+    {
+      // the latency, certificate and message kernels read the key cache
+      KeyUse keys(sl, sl.lat || L.nc || msgs);
+      clk.mark(coa_q::Launch::ENQ_PIN);
+      if (L.nv && sl.lat)
+        rc = coa_lat_verify_device(sl.dev, d + p.v_recs.at, L.nv, out_words(p.o_sigs), sl.s);
+      else if (L.nv)
+        rc = coa_ed25519_verify_strict_many_device(sl.dev, d + p.v_msgs.at, 32, d + p.v_pks.at, d + p.v_sigs.at, L.nv,
+                                                   dout + p.o_sigs.at, sl.ws, sl.s);
+      if (rc == COA_OK && L.nc) {
+        // key order for a large window (COA_QUEUE_KEYSORT): see
+        // coa_certificate_verify_many_device_order
+        const CertIn c = cert_view(d, p.cert);
+        rc = coa_certificate_verify_many_device_order(sl.dev, c.hdr_data, c.hdr_off, c.ids, c.origins, c.hsigs,
+                                                      c.rounds, c.vpks, c.vsigs, c.voff, L.nc, L.nvotes,
+                                                      out_words(p.o_certs), sl.ws, sl.s, keysort_ ? 1 : 0);
+      }
+      uint32_t* d_mst = out_words(p.o_msgs);  // the headers' status words, then the votes'
+      if (rc == COA_OK && msg_lat) {
+        const CoaMsgLatIn in = msg_lat_in(d, p, L);
+        rc = coa_msg_lat_verify_device(sl.dev, &in, d_mst, sl.s);
+      } else if (rc == COA_OK && msgs) {
+        const MsgIn h = msg_view(d, p.hdr, false), v = msg_view(d, p.vote, true);
+        if (L.nhd)
+          rc = coa_header_verify_many_device(sl.dev, h.hdr_data, h.hdr_off, h.ids, h.authors, h.sigs, L.nhd, d_mst,
+                                             sl.ws, sl.s);
+        if (rc == COA_OK && L.nvt)
+          rc = coa_vote_verify_many_device(sl.dev, v.ids, v.rounds, v.origins, v.authors, v.sigs, L.nvt,
+                                           d_mst + L.nhd, sl.ws, sl.s);
+      }
+      if (rc == COA_OK && L.nd)
+        rc = coa_sha512_many_device(sl.dev, d + p.d_data.at, reinterpret_cast<const uint64_t*>(d + p.d_off.at), L.nd,
+                                    dout + p.o_digs.at, sl.s);
     }
-    uint32_t* d_mst = reinterpret_cast<uint32_t*>(dout + sl.o_m);
-    if (rc == COA_OK && msg_lat) {
-      rc = coa_msg_lat_verify_device(sl.dev, &msg_in, d_mst, sl.s);
-    } else if (rc == COA_OK && msgs) {
-      if (L.nhd)
-        rc = coa_header_verify_many_device(sl.dev, msg_in.hdr_data, msg_in.hdr_off, msg_in.hids, msg_in.hauthors,
-                                           msg_in.hsigs, L.nhd, d_mst, sl.ws, sl.s);
-      if (rc == COA_OK && L.nvt)
-        rc = coa_vote_verify_many_device(sl.dev, msg_in.vids, msg_in.vrounds, msg_in.vorigins, msg_in.vauthors,
-                                         msg_in.vsigs, L.nvt, d_mst + L.nhd, sl.ws, sl.s);
-    }
-    if (rc == COA_OK && L.nd)
-      rc = coa_sha512_many_device(sl.dev, d + i_dd, reinterpret_cast<const uint64_t*>(d + i_do), L.nd, dout + sl.o_d,
-                                  sl.s);
-    coa_keycache_use(nullptr);
-    mark(coa_q::Launch::ENQ_LAUNCH);
+    clk.mark(coa_q::Launch::ENQ_LAUNCH);
     if (rc != COA_OK) return rc;
-    if (hipMemcpyAsync(sl.hout, dout, out_bytes, hipMemcpyDeviceToHost, sl.s) != hipSuccess) return COA_EHIP;
-    mark(coa_q::Launch::ENQ_D2H);
-    if (hipEventRecord(sl.ev, sl.s) != hipSuccess) return COA_EHIP;
-    mark(coa_q::Launch::ENQ_EVENT);
-    return COA_OK;
+    if (hipMemcpyAsync(sl.hout, dout, p.out_total, hipMemcpyDeviceToHost, sl.s) != hipSuccess) return COA_EHIP;
+    clk.mark(coa_q::Launch::ENQ_D2H);
+    return record(sl, clk);
   }
 
   // Waits for the slot's work (a failed enqueue drains its stream, keeping
@@ -821,8 +770,8 @@ class HipBackend : public coa_q::Backend {
     const auto t_wait = std::chrono::steady_clock::now();
     if (sl.launched) {
       (void)hipSetDevice(sl.dev);
-      if (L.rc == COA_OK && (sl.inl || sl.cpub || sl.mpub)) {
-        L.rc = poll_words(sl, sl.inl ? L.nv : sl.cpub ? L.nc : L.nhd + L.nvt);
+      if (L.rc == COA_OK && sl.route != coa_q::ROUTE_STAGED) {
+        L.rc = poll_words(sl);
       } else if (L.rc == COA_OK) {
         if (hipEventSynchronize(sl.ev) != hipSuccess) L.rc = COA_EHIP;
       } else {
@@ -832,34 +781,7 @@ class HipBackend : public coa_q::Backend {
     }
     const auto t_scatter = std::chrono::steady_clock::now();
     L.stage_ns[COA_QSTAGE_DEVICE_WAIT] += ns_between(t_wait, t_scatter);
-    if (L.rc == COA_OK) {
-      const uint8_t* h = static_cast<const uint8_t*>(sl.hout);
-      size_t v = 0, c = 0, dn = 0, mh = 0, mt = 0;
-      const uint32_t* mst = sl.mpub ? sl.lres : reinterpret_cast<const uint32_t*>(h + sl.o_m);
-      for (coa_q::Window* w : L.parts) {
-        scatter_messages(*w, mst + mh, mst + L.nhd + mt);
-        mh += w->nhd;
-        mt += w->nvt;
-        if (w->nv && sl.lat) {
-          const uint32_t* words = (sl.inl ? sl.lres : reinterpret_cast<const uint32_t*>(h + sl.o_v)) + v;
-          for (size_t i = 0; i < w->nv; i++) w->v_out[i] = (uint8_t)(words[i] & 0xffu);
-        } else if (w->nv) {
-          std::memcpy(w->v_out.data(), h + sl.o_v + v, w->nv);
-        }
-        for (size_t i = 0; i < w->nd; i++) std::memcpy(&w->d_out[i * 32], h + sl.o_d + (dn + i) * 64, 32);
-        if (w->nc && sl.cpub) {
-          uint32_t st[COA_LAT_RES_WORDS];
-          for (size_t i = 0; i < w->nc; i++) st[i] = sl.lres[c + i] & 0xffu;  // the tag off
-          scatter_certs(*w, st);
-        } else if (w->nc) {
-          scatter_certs(*w, reinterpret_cast<const uint32_t*>(h + sl.o_c) + c);
-        }
-        w->g_defer = w->ng > 0;
-        v += w->nv;
-        c += w->nc;
-        dn += w->nd;
-      }
-    }
+    if (L.rc == COA_OK) coa_q::window_scatter(L, sl.pack, static_cast<const uint8_t*>(sl.hout), sl.route, sl.lres);
     if (sl.keys) {
       coa_keycache_unpin(sl.keys);
       sl.keys = nullptr;
@@ -867,13 +789,13 @@ class HipBackend : public coa_q::Backend {
     L.stage_ns[COA_QSTAGE_SCATTER] += ns_between(t_scatter, std::chrono::steady_clock::now());
   }
 
-  // An inline latency window's n result words, polled for the slot's tag.
-  // A kernel that ended without publishing (a fault) ends the wait through
-  // the slot's event; a bound stops a hang.  On failure the stream is
-  // drained before the slot is reused.
-  static int poll_words(Slot& sl, size_t n) {
+  // A publish route's result words (Slot::npub of them), polled for the
+  // slot's tag.  A kernel that ended without publishing (a fault) ends the
+  // wait through the slot's event; a bound stops a hang.  On failure the
+  // stream is drained before the slot is reused.
+  static int poll_words(Slot& sl) {
     const auto t0 = std::chrono::steady_clock::now();
-    for (size_t i = 0; i < n; i++) {
+    for (size_t i = 0; i < sl.npub; i++) {
       const volatile uint32_t* w = sl.lres + i;
       for (uint64_t spin = 0; (*w >> 8) != sl.ltag; spin++) {
         if ((spin & 1023) != 1023) continue;
@@ -888,39 +810,6 @@ class HipBackend : public coa_q::Backend {
     return COA_OK;
   }
 
-  // Raw message status words (a published word's tag ignored) -> the
-  // headers' COA_CERT_BAD_HEADER_* bits and the votes' verdicts; a message by an
-  // author outside the committee is left open for resolve(), a header's
-  // digest bit kept.
-  static void scatter_messages(coa_q::Window& w, const uint32_t* hst, const uint32_t* vst) {
-    w.m_defer.clear();
-    for (size_t i = 0; i < w.nhd; i++) {
-      const bool open = (hst[i] & COA_CST_UNCACHED) != 0;
-      if (open) w.m_defer.push_back((uint32_t)i);
-      w.hd_out[i] = (uint8_t)(hst[i] & (open ? 1u : 3u));
-    }
-    for (size_t i = 0; i < w.nvt; i++) {
-      if (vst[i] & COA_CST_UNCACHED) w.m_defer.push_back((uint32_t)(w.nhd + i));
-      w.vt_out[i] = (vst[i] & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
-    }
-  }
-
-  // Raw certificate status words -> COA_CERT_* bits; the certificates the
-  // fused kernel could not decide alone keep their raw words and are left
-  // open for resolve().
-  static void scatter_certs(coa_q::Window& w, const uint32_t* st) {
-    w.c_raw.assign(st, st + w.nc);
-    w.c_defer.clear();
-    for (size_t c = 0; c < w.nc; c++) {
-      // exactly the words coa_certificate_resolve_raw re-decides: a key
-      // outside the committee, or inconclusive votes not already bad
-      const bool open = (st[c] & COA_CST_UNCACHED) ||
-                        ((st[c] & COA_CST_VOTES_INCONCLUSIVE) && !(st[c] & COA_CST_BAD_VOTES));
-      if (open) w.c_defer.push_back((uint32_t)c);
-      w.c_out[c] = (uint8_t)(st[c] & 7u);
-    }
-  }
-
  public:
   // The open certificates of every window in `ws` in one exact pass
   // (coa_certificate_resolve_raw: header signature by verify_strict and votes
@@ -928,85 +817,31 @@ class HipBackend : public coa_q::Backend {
   // for inconclusive votes -- never the fused kernel again), and every bare
   // vote batch in one coa_ed25519_verify_batch_groups call.
   int resolve(const std::vector<coa_q::Window*>& ws) override {
-    std::vector<uint8_t> ids, org, hs, vp, vs;
-    std::vector<uint64_t> rd, vo{0};
-    std::vector<uint32_t> raw;
-    std::vector<uint8_t> gm, gp, gs;
-    std::vector<uint64_t> go{0};
-    for (const coa_q::Window* w : ws) {
-      for (uint32_t c : w->c_defer) {
-        const coa_q::Window::CertRef& r = w->c_refs[c];
-        ids.insert(ids.end(), r.id, r.id + 32);
-        org.insert(org.end(), r.origin, r.origin + 32);
-        hs.insert(hs.end(), r.hsig, r.hsig + 64);
-        rd.push_back(r.round);
-        vp.insert(vp.end(), r.vpks, r.vpks + r.nv * 32);
-        vs.insert(vs.end(), r.vsigs, r.vsigs + r.nv * 64);
-        vo.push_back(vp.size() / 32);
-        raw.push_back(w->c_raw[c]);
-      }
-      if (w->g_defer) {
-        gm.insert(gm.end(), w->g_msgs.begin(), w->g_msgs.end());
-        gp.insert(gp.end(), w->g_pks.begin(), w->g_pks.end());
-        gs.insert(gs.end(), w->g_sigs.begin(), w->g_sigs.end());
-        for (size_t g = 1; g <= w->ng; g++) go.push_back(go.back() + (w->g_offs[g] - w->g_offs[g - 1]));
-      }
-    }
+    coa_q::Deferred d = coa_q::gather_deferred(ws);
     // the open messages: verify_strict through the uncached path, the votes
-    // over Vote::digest (coa_message_resolve_raw)
-    std::vector<uint8_t> mi[2], mo, ma[2], ms[2];  // [0] headers, [1] votes
-    std::vector<uint64_t> mr;
-    std::vector<uint32_t> mraw[2];
-    for (const coa_q::Window* w : ws)
-      for (uint32_t m : w->m_defer) {
-        const bool vote = m >= w->nhd;
-        const size_t i = vote ? m - w->nhd : m;
-        const uint8_t* id = (vote ? w->vt_ids : w->hd_ids).data() + i * 32;
-        const uint8_t* au = (vote ? w->vt_authors : w->hd_authors).data() + i * 32;
-        const uint8_t* sg = (vote ? w->vt_sigs : w->hd_sigs).data() + i * 64;
-        mi[vote].insert(mi[vote].end(), id, id + 32);
-        ma[vote].insert(ma[vote].end(), au, au + 32);
-        ms[vote].insert(ms[vote].end(), sg, sg + 64);
-        if (vote) {
-          mo.insert(mo.end(), w->vt_origins.data() + i * 32, w->vt_origins.data() + i * 32 + 32);
-          mr.push_back(w->vt_rounds[i]);
-        }
-        mraw[vote].push_back(COA_CST_UNCACHED | (vote ? 0u : (uint32_t)(w->hd_out[i] & 1u)));
-      }
+    // over Vote::digest
     for (int vote = 0; vote < 2; vote++) {
-      if (mraw[vote].empty()) continue;
-      const int rc = coa_message_resolve_raw(mi[vote].data(), vote ? mr.data() : nullptr, vote ? mo.data() : nullptr,
-                                             ma[vote].data(), ms[vote].data(), mraw[vote].size(), mraw[vote].data());
+      if (d.m_raw[vote].empty()) continue;
+      const int rc = coa_message_resolve_raw(d.m_ids[vote].data(), vote ? d.m_rounds.data() : nullptr,
+                                             vote ? d.m_origins.data() : nullptr, d.m_authors[vote].data(),
+                                             d.m_sigs[vote].data(), d.m_raw[vote].size(), d.m_raw[vote].data());
       if (rc != COA_OK) return rc;
     }
-    size_t mj[2] = {0, 0};
-    for (coa_q::Window* w : ws)
-      for (uint32_t m : w->m_defer) {
-        const bool vote = m >= w->nhd;
-        const uint32_t st = mraw[vote][mj[vote]++];
-        if (vote)
-          w->vt_out[m - w->nhd] = (st & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
-        else
-          w->hd_out[m] = (uint8_t)(st & 3u);
-      }
-    if (!raw.empty()) {
-      std::vector<uint8_t> out(raw.size(), 7);
-      const int rc = coa_certificate_resolve_raw(ids.data(), org.data(), hs.data(), rd.data(), vp.data(), vs.data(),
-                                                 vo.data(), raw.size(), raw.data(), out.data());
+    coa_q::put_messages(ws, d);
+    if (!d.c_raw.empty()) {
+      std::vector<uint8_t> out(d.c_raw.size(), 7);
+      const int rc = coa_certificate_resolve_raw(d.c_ids.data(), d.c_origins.data(), d.c_hsigs.data(),
+                                                 d.c_rounds.data(), d.c_vpks.data(), d.c_vsigs.data(),
+                                                 d.c_voff.data(), d.c_raw.size(), d.c_raw.data(), out.data());
       if (rc != COA_OK) return rc;
-      size_t j = 0;
-      for (coa_q::Window* w : ws)
-        for (uint32_t c : w->c_defer) w->c_out[c] = out[j++];
+      coa_q::put_certs(ws, out.data());
     }
-    if (go.size() > 1) {
-      std::vector<uint8_t> out(go.size() - 1, 1);
-      const int rc = coa_ed25519_verify_batch_groups(gm.data(), gp.data(), gs.data(), go.data(), go.size() - 1,
-                                                     out.data(), 0);
+    if (d.g_off.size() > 1) {
+      std::vector<uint8_t> out(d.g_off.size() - 1, 1);
+      const int rc = coa_ed25519_verify_batch_groups(d.g_msgs.data(), d.g_pks.data(), d.g_sigs.data(),
+                                                     d.g_off.data(), d.g_off.size() - 1, out.data(), 0);
       if (rc != COA_OK) return rc;
-      size_t j = 0;
-      for (coa_q::Window* w : ws)
-        if (w->g_defer)
-          for (size_t g = 0; g < w->ng; g++) w->g_out[g] = out[j++];
+      coa_q::put_groups(ws, out.data());
     }
     return COA_OK;
   }

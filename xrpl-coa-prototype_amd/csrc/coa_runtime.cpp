@@ -2555,12 +2555,7 @@ void coa_keycache_unpin(void* pin) { delete static_cast<KeySetP*>(pin); }
 
 void coa_keycache_use(void* pin) { t_keys_pinned = static_cast<const KeySetP*>(pin); }
 
-void coa_copy_segments(const CoaCopySeg* segs, size_t n) {
-  std::vector<Seg> v;
-  v.reserve(n);
-  for (size_t i = 0; i < n; i++) v.push_back({segs[i].dst, segs[i].src, segs[i].bytes});
-  CopyPool::get().copy(v);
-}
+void coa_copy_segments(const Seg* segs, size_t n) { CopyPool::get().copy(segs, n); }
 
 size_t coa_lat_max(void) { return lat_max(); }
 
@@ -2612,29 +2607,20 @@ int coa_lat_verify_inline(int device, const uint8_t* h_records, size_t n, uint32
 }
 
 int coa_certificate_verify_publish(int device, const uint8_t* h_base, uint8_t* d_base, size_t in_bytes,
-                                   const CoaCertOffsets* off, size_t n, size_t n_votes, uint32_t* d_ctr,
-                                   uint32_t* host_res, uint32_t tag, void* stream) {
+                                   const CertPack* p, size_t n, size_t n_votes, uint32_t* d_ctr, uint32_t* host_res,
+                                   uint32_t tag, void* stream) {
   const int rc = ensure_init();
   if (rc != COA_OK) return rc;
   if (n == 0) return COA_OK;
   if (n > 64 || cert_lanes(n + n_votes) != 64) return 1;  // not the latency kernel's size: nothing enqueued
-  if (!h_base || !d_base || !off || !d_ctr || !host_res || tag == 0) return fail(COA_EINVAL, "null argument");
+  if (!h_base || !d_base || !p || !d_ctr || !host_res || tag == 0) return fail(COA_EINVAL, "null argument");
   Dev* d = dev_by_id(device);
   if (!d) return fail(COA_EINVAL, "device not opened by coa_init");
   HIP_TRY(hipSetDevice(device));
   hipStream_t s = stream ? (hipStream_t)stream : d->stream;
-  const CertIn in{h_base + off->hdr,
-                  reinterpret_cast<const uint64_t*>(h_base + off->hoff),
-                  h_base + off->ids,
-                  h_base + off->origins,
-                  h_base + off->hsigs,
-                  reinterpret_cast<const uint64_t*>(h_base + off->rounds),
-                  h_base + off->vpks,
-                  h_base + off->vsigs,
-                  reinterpret_cast<const uint64_t*>(h_base + off->voff)};
   const KeySetP ks = keys_now(*d);  // pinned (the queue) or current; see coa_lat_verify_device
   static thread_local CertInl ci;
-  if (!env_is("COA_CERT_INLINE", "0") && cert_inl_build(ci, in, 0, n)) {
+  if (!env_is("COA_CERT_INLINE", "0") && cert_inl_build(ci, cert_view(h_base, *p), 0, n)) {
     CertArgs& a = ci.a;
     a = cert_args_packed(*d, *ks, nullptr, CertPack{}, n, n_votes);
     a.status = d_ctr + 1;
@@ -2645,11 +2631,7 @@ int coa_certificate_verify_publish(int device, const uint8_t* h_base, uint8_t* d
     return trail_keys(*d, ks, s);
   }
   HIP_TRY(hipMemcpyAsync(d_base, h_base, in_bytes, hipMemcpyHostToDevice, s));
-  CertArgs a = cert_args(d_base + off->hdr, reinterpret_cast<const uint64_t*>(d_base + off->hoff), d_base + off->ids,
-                         d_base + off->origins, d_base + off->hsigs,
-                         reinterpret_cast<const uint64_t*>(d_base + off->rounds), d_base + off->vpks,
-                         d_base + off->vsigs, reinterpret_cast<const uint64_t*>(d_base + off->voff), n, n_votes);
-  key_args(a, *d, *ks);
+  CertArgs a = cert_args_packed(*d, *ks, d_base, *p, n, n_votes);
   a.status = d_ctr + 1;
   a.host_res = host_res;
   a.done_ctr = d_ctr;

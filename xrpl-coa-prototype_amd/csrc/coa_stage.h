@@ -11,6 +11,14 @@
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Raw status bits of the certificate and message kernels (the low three are
+// the public COA_CERT_BAD_* bits of include/coa_verify.h).
+#define COA_CST_BAD_HEADER_ID 1u
+#define COA_CST_BAD_HEADER_SIG 2u
+#define COA_CST_BAD_VOTES 4u
+#define COA_CST_VOTES_INCONCLUSIVE 8u  // some vote failed its own equation, or a key has torsion
+#define COA_CST_UNCACHED 16u           // author or a voter is not in the registered committee
+
 // One section of a block: `bytes` at offset `at` (bytes 0: not in this block).
 struct Sec {
   size_t at = 0, bytes = 0;
@@ -65,6 +73,13 @@ struct CertPack {
   Sec status, hoff, voff, ids, origins, hsigs, rounds, vpks, vsigs, hdata, pcounts, proto, verd;
   size_t total = 0;
 };
+
+// The arrays of a block laid out as p at address base (host or device).
+inline CertIn cert_view(const uint8_t* base, const CertPack& p) {
+  auto u64 = [base](const Sec& s) { return reinterpret_cast<const uint64_t*>(base + s.at); };
+  return {base + p.hdata.at, u64(p.hoff), base + p.ids.at, base + p.origins.at, base + p.hsigs.at,
+          u64(p.rounds),     base + p.vpks.at, base + p.vsigs.at, u64(p.voff)};
+}
 
 // inl: the record inline in the latency kernel's arguments -- 16-byte
 // sections and no status words (they live in the context's counter block);
@@ -171,6 +186,14 @@ struct MsgPack {
   Sec status, ids, authors, sigs, rounds, origins, hoff, hdata, pcounts, proto, verd;
   size_t total = 0;
 };
+
+// As cert_view.  The arrays the shape does not have point at the block's
+// start and are not read.
+inline MsgIn msg_view(const uint8_t* base, const MsgPack& p, bool votes) {
+  auto u64 = [base](const Sec& s) { return reinterpret_cast<const uint64_t*>(base + s.at); };
+  return {base + p.hdata.at, u64(p.hoff),       base + p.ids.at,  u64(p.rounds),
+          base + p.origins.at, base + p.authors.at, base + p.sigs.at, votes};
+}
 
 inline MsgPack msg_layout(size_t n, bool votes, size_t hbytes, bool verdicts) {
   MsgPack p;
