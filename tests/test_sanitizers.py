@@ -160,3 +160,67 @@ def test_cpu_path_asan_ubsan():
     out = _run([exe, vec], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=1",
                             "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
     assert "cpu path ok" in out and " 0 bad" in out
+
+
+def _cpu_vote(path):
+    """tests/sanitize/cpu_first_call.cpp's valid vote: id | round LE | origin |
+    author | signature over Vote::digest, signed by the oracle."""
+    import hashlib
+    import struct
+
+    import ed25519_ref as o
+
+    seed = hashlib.sha512(b"cpu-first-call-vote").digest()[:32]
+    id_, rnd, origin = hashlib.sha512(b"id").digest()[:32], 7, o.public_key(hashlib.sha512(b"origin").digest()[:32])
+    digest = hashlib.sha512(id_ + struct.pack("<Q", rnd) + origin).digest()[:32]
+    with open(path, "wb") as f:
+        f.write(id_ + struct.pack("<Q", rnd) + origin + o.public_key(seed) + o.sign(seed, digest))
+    return path
+
+
+def _first_call_runs(exe, runs, env):
+    d = os.path.dirname(exe)
+    vec, vote = _cpu_vectors(os.path.join(d, "cpu_vectors.bin")), _cpu_vote(os.path.join(d, "cpu_vote.bin"))
+    for _ in range(runs):  # fresh processes: each has one first call
+        assert "first calls ok: 16 threads, 0 wrong" in _run([exe, "16", vec, vote], env)
+
+
+FIRST_CALL = [os.path.join(CSRC, "coa_cpu.cpp"), os.path.join(ROOT, "tests", "sanitize", "cpu_first_call.cpp")]
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang (TSan runtime) not present")
+def test_cpu_first_call_tsan():
+    """Sixteen threads' first calls into the CPU path at once, every entry that
+    needs the curve constants among them: no race on the constants (the
+    detector: the globals this replaced raced in every process), every valid
+    input accepted and every forged one rejected."""
+    exe = _build(os.path.join(ROOT, "tests", "sanitize", "_build", "cpu_first_call_tsan"), FIRST_CALL,
+                 ["-fsanitize=thread"], cxx=CLANG)
+    _first_call_runs(exe, 10, {"TSAN_OPTIONS": "halt_on_error=1"})
+
+
+def test_cpu_first_call_asan_ubsan():
+    """The same first calls under ASan + UBSan."""
+    exe = _build(os.path.join(ROOT, "tests", "sanitize", "_build", "cpu_first_call_asan"), FIRST_CALL,
+                 ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    _first_call_runs(exe, 5, {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=1",
+                              "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+
+
+def test_cpu_first_call_plain():
+    """And as a plain -O2 build, 200 processes: a backstop (a partly built
+    table accepted forged signatures in about 1 process of 200), not the
+    proof -- that is the ThreadSanitizer form."""
+    exe = _build(os.path.join(ROOT, "tests", "sanitize", "_build", "cpu_first_call_plain"), FIRST_CALL, ["-O2"])
+    _first_call_runs(exe, 200, {})
+
+
+def test_cpu_points_fail_closed_asan_ubsan():
+    """coa_cpu.cpp's point predicates reject a point with Z == 0 and answer as
+    before for real ones; B's table is [1..8]B; curve() is one value."""
+    exe = _build(os.path.join(ROOT, "tests", "sanitize", "_build", "cpu_points_asan"),
+                 [os.path.join(ROOT, "tests", "sanitize", "cpu_points_driver.cpp")],
+                 ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wno-unused-function"])
+    out = _run([exe], {"ASAN_OPTIONS": "detect_leaks=1:abort_on_error=1",
+                       "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    assert "cpu points: 0 bad" in out

@@ -30,15 +30,16 @@
 // points with the a = -1 formulas; signed radix-16 windows for every scalar,
 // one shared doubling chain (Straus) for the two-term verify and for the batch
 // equation; scalars reduced mod l bit-serially; the curve constants (d,
-// sqrt(-1), B) derived at first use from their definitions.  Work is spread
+// sqrt(-1), B, [1..8]B) one immutable Curve built from their definitions,
+// published whole (curve()) and handed down by every entry.  Work is spread
 // over std::threads in contiguous index ranges.
 #include <sys/random.h>
 
 #include <algorithm>
 #include <cerrno>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -49,6 +50,21 @@ namespace {
 
 using u128 = unsigned __int128;
 constexpr uint64_t kM51 = (uint64_t(1) << 51) - 1;
+
+// nw little-endian 64-bit words
+void load_words(uint64_t* w, const uint8_t* s, int nw) {
+  for (int i = 0; i < nw; i++) {
+    w[i] = 0;
+    for (int b = 7; b >= 0; b--) w[i] = w[i] << 8 | s[8 * i + b];
+  }
+}
+
+// off[0..n] never decreases
+bool offsets_monotone(const uint64_t* off, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
 
 // ------------------------------------------------------------------ SHA-512
 struct Sha512 {
@@ -229,17 +245,9 @@ Fe fe_sqn(Fe a, int n) {
 // mod p (dalek's FieldElement::from_bytes)
 Fe fe_load(const uint8_t s[32]) {
   uint64_t w[4];
-  for (int i = 0; i < 4; i++) {
-    w[i] = 0;
-    for (int b = 7; b >= 0; b--) w[i] = w[i] << 8 | s[8 * i + b];
-  }
-  Fe f;
-  f.v[0] = w[0] & kM51;
-  f.v[1] = (w[0] >> 51 | w[1] << 13) & kM51;
-  f.v[2] = (w[1] >> 38 | w[2] << 26) & kM51;
-  f.v[3] = (w[2] >> 25 | w[3] << 39) & kM51;
-  f.v[4] = (w[3] >> 12) & kM51;
-  return f;
+  load_words(w, s, 4);
+  return Fe{{w[0] & kM51, (w[0] >> 51 | w[1] << 13) & kM51, (w[1] >> 38 | w[2] << 26) & kM51,
+             (w[2] >> 25 | w[3] << 39) & kM51, (w[3] >> 12) & kM51}};
 }
 
 // the canonical encoding (value fully reduced below p)
@@ -304,11 +312,7 @@ Fe fe_pow_p58(const Fe& z) {  // z^((p-5)/8) = z^(2^252 - 3)
   return fe_mul(fe_sqn(z250, 2), z);
 }
 
-// --------------------------------------------------------- curve constants
-struct Consts {
-  Fe d, d2, sqrtm1;
-};
-
+// ------------------------------------------------------------------ points
 struct Pt {  // extended: x = X/Z, y = Y/Z, x y = T/Z
   Fe X, Y, Z, T;
 };
@@ -317,13 +321,10 @@ struct Cached {  // Y+X, Y-X, 2Z, 2dT of an addend
   Fe ypx, ymx, z2, t2d;
 };
 
-const Consts& consts();
-
 Pt pt_identity() { return Pt{fe_small(0), fe_small(1), fe_small(1), fe_small(0)}; }
 
-Cached pt_cache(const Pt& p) {
-  const Consts& c = consts();
-  return Cached{fe_add(p.Y, p.X), fe_sub(p.Y, p.X), fe_add(p.Z, p.Z), fe_mul(p.T, c.d2)};
+Cached pt_cache(const Pt& p, const Fe& d2) {
+  return Cached{fe_add(p.Y, p.X), fe_sub(p.Y, p.X), fe_add(p.Z, p.Z), fe_mul(p.T, d2)};
 }
 
 // p + q (neg: p - q), a = -1 unified addition
@@ -348,79 +349,92 @@ Pt pt_double(const Pt& p) {
   return Pt{fe_mul(e, f), fe_mul(g, h), fe_mul(f, g), fe_mul(e, h)};
 }
 
-bool pt_is_identity(const Pt& p) { return fe_is_zero(p.X) && fe_equal(p.Y, p.Z); }
-
-bool pt_same(const Pt& p, const Pt& q) {
-  return fe_equal(fe_mul(p.X, q.Z), fe_mul(q.X, p.Z)) && fe_equal(fe_mul(p.Y, q.Z), fe_mul(q.Y, p.Z));
+// [1..8]P
+void pt_table(const Pt& p, Cached tab[8], const Fe& d2) {
+  tab[0] = pt_cache(p, d2);
+  Pt m = p;
+  for (int i = 1; i < 8; i++) {
+    m = pt_add(m, tab[0], false);
+    tab[i] = pt_cache(m, d2);
+  }
 }
 
-// [8]P == identity: the eight torsion points (P itself on the curve)
-bool pt_small_order(const Pt& p) { return pt_is_identity(pt_double(pt_double(pt_double(p)))); }
+// The accept decisions rest on these three.  Z == 0 is no point of the curve
+// and never arises from valid state; should a bug ever make one, each answers
+// in the rejecting direction.
+bool pt_is_identity(const Pt& p) { return fe_is_zero(p.X) && !fe_is_zero(p.Z) && fe_equal(p.Y, p.Z); }
+
+bool pt_same(const Pt& p, const Pt& q) {
+  return !fe_is_zero(p.Z) && !fe_is_zero(q.Z) && fe_equal(fe_mul(p.X, q.Z), fe_mul(q.X, p.Z)) &&
+         fe_equal(fe_mul(p.Y, q.Z), fe_mul(q.Y, p.Z));
+}
+
+// [8]P == identity: the eight torsion points (P itself on the curve).  Small
+// order rejects, so a degenerate P or [8]P counts as small order
+bool pt_small_order(const Pt& p) {
+  const Pt e = pt_double(pt_double(pt_double(p)));
+  return fe_is_zero(p.Z) || fe_is_zero(e.Z) || pt_is_identity(e);
+}
 
 // curve25519-dalek's sqrt_ratio_i: (was_square, r) with r = +sqrt(u/v) or
 // +sqrt(i u/v), r non-negative
-bool sqrt_ratio_i(const Fe& u, const Fe& v, Fe& r) {
-  const Consts& k = consts();
+bool sqrt_ratio_i(const Fe& u, const Fe& v, const Fe& sqrtm1, Fe& r) {
   const Fe v3 = fe_mul(fe_sq(v), v);
   const Fe v7 = fe_mul(fe_sq(v3), v);
   r = fe_mul(fe_mul(u, v3), fe_pow_p58(fe_mul(u, v7)));
   const Fe check = fe_mul(v, fe_sq(r));
   const Fe mu = fe_neg(u);
   const bool correct = fe_equal(check, u), flipped = fe_equal(check, mu),
-             flipped_i = fe_equal(check, fe_mul(mu, k.sqrtm1));
-  if (flipped || flipped_i) r = fe_mul(r, k.sqrtm1);
+             flipped_i = fe_equal(check, fe_mul(mu, sqrtm1));
+  if (flipped || flipped_i) r = fe_mul(r, sqrtm1);
   if (fe_is_negative(r)) r = fe_neg(r);
   return correct || flipped;
 }
 
 // CompressedEdwardsY::decompress: false when x^2 = (y^2 - 1) / (d y^2 + 1)
 // has no root; the sign bit is applied even to x = 0
-bool pt_decompress(const uint8_t s[32], Pt& p) {
-  const Consts& k = consts();
+bool pt_decompress(const uint8_t s[32], const Fe& d, const Fe& sqrtm1, Pt& p) {
   p.Y = fe_load(s);
   p.Z = fe_small(1);
   const Fe yy = fe_sq(p.Y);
   const Fe u = fe_sub(yy, p.Z);
-  const Fe v = fe_add(fe_mul(yy, k.d), p.Z);
-  if (!sqrt_ratio_i(u, v, p.X)) return false;
+  const Fe v = fe_add(fe_mul(yy, d), p.Z);
+  if (!sqrt_ratio_i(u, v, sqrtm1, p.X)) return false;
   if (s[31] >> 7) p.X = fe_neg(p.X);
   p.T = fe_mul(p.X, p.Y);
   return true;
 }
 
-Consts* g_consts = nullptr;
-Pt g_base;
-Cached g_base_tab[8];  // [1..8]B
-std::once_flag g_once;
+// --------------------------------------------------------- curve constants
+struct Curve {
+  Fe d, d2, sqrtm1;
+  Pt base;
+  Cached base_tab[8];  // [1..8]B
+};
 
-void init_consts() {
-  static Consts c;
+Curve make_curve() {
+  Curve k;
   // d = -121665 / 121666
-  c.d = fe_mul(fe_neg(fe_small(121665)), fe_inverse(fe_small(121666)));
-  c.d2 = fe_add(c.d, c.d);
+  k.d = fe_mul(fe_neg(fe_small(121665)), fe_inverse(fe_small(121666)));
+  k.d2 = fe_add(k.d, k.d);
   // sqrt(-1) = 2^((p-1)/4); (p-1)/4 = 2^253 - 5 = (2^250 - 1) * 8 + 3
   Fe two250, two11;
   fe_chain250(fe_small(2), two250, two11);
-  c.sqrtm1 = fe_mul(fe_sqn(two250, 3), fe_mul(fe_small(2), fe_small(4)));
-  g_consts = &c;
-  // B: y = 4/5, x even -- the encoding 0x58 0x66 ... 0x66
+  k.sqrtm1 = fe_mul(fe_sqn(two250, 3), fe_mul(fe_small(2), fe_small(4)));
+  // B: y = 4/5, x even -- the encoding 0x58 0x66 ... 0x66; no B, no answers
   uint8_t b[32];
   std::memset(b, 0x66, 32);
   b[0] = 0x58;
-  if (!pt_decompress(b, g_base)) std::abort();
-  Pt m = g_base;
-  for (int i = 0; i < 8; i++) {
-    g_base_tab[i] = pt_cache(m);
-    m = pt_add(m, g_base_tab[0], false);
-  }
+  if (!pt_decompress(b, k.d, k.sqrtm1, k.base)) std::abort();
+  pt_table(k.base, k.base_tab, k.d2);
+  return k;
 }
 
-const Consts& consts() {
-  if (!g_consts) std::call_once(g_once, init_consts);
-  return *g_consts;
+// the one published value: nobody can see it before it is whole
+const Curve& curve() {
+  static const Curve k = make_curve();
+  return k;
 }
-
-void ensure_consts() { (void)consts(); }
 
 // ------------------------------------------------------------ scalars mod l
 // l = 2^252 + 27742317777372353535851937790883648493, little-endian 64-bit words
@@ -458,13 +472,6 @@ Sc sc_mod(const uint64_t* x, int nw) {
     if (sc_ge_l(r.w)) sc_sub_l(r.w);
   }
   return r;
-}
-
-void load_words(uint64_t* w, const uint8_t* s, int nw) {
-  for (int i = 0; i < nw; i++) {
-    w[i] = 0;
-    for (int b = 7; b >= 0; b--) w[i] = w[i] << 8 | s[8 * i + b];
-  }
 }
 
 Sc sc_from_hash(const uint8_t h[64]) {
@@ -523,16 +530,6 @@ void sc_digits16(const Sc& s, int8_t d[64]) {
   d[63] = (int8_t)(d[63] + carry);
 }
 
-// [1..8]P
-void pt_table(const Pt& p, Cached tab[8]) {
-  tab[0] = pt_cache(p);
-  Pt m = p;
-  for (int i = 1; i < 8; i++) {
-    m = pt_add(m, tab[0], false);
-    tab[i] = pt_cache(m);
-  }
-}
-
 void add_digit(Pt& q, const Cached* tab, int d) {
   if (d > 0) q = pt_add(q, tab[d - 1], false);
   if (d < 0) q = pt_add(q, tab[-d - 1], true);
@@ -570,15 +567,15 @@ Sc challenge(const uint8_t* R, const uint8_t* A, const uint8_t* msg, size_t msg_
 }
 
 // ed25519-dalek 1.0.1 PublicKey::verify_strict: 0 Ok / 1 Err
-int verify_strict_one(const uint8_t* msg, size_t msg_len, const uint8_t* pk, const uint8_t* sig) {
+int verify_strict_one(const Curve& cv, const uint8_t* msg, size_t msg_len, const uint8_t* pk, const uint8_t* sig) {
   Sc s;
   if (!scalar_canonical(sig + 32, s)) return 1;
   Pt A, R;
-  if (!pt_decompress(pk, A) || !pt_decompress(sig, R)) return 1;
+  if (!pt_decompress(pk, cv.d, cv.sqrtm1, A) || !pt_decompress(sig, cv.d, cv.sqrtm1, R)) return 1;
   if (pt_small_order(A) || pt_small_order(R)) return 1;
   const Sc k = challenge(sig, pk, msg, msg_len);
   Cached atab[8];
-  pt_table(A, atab);
+  pt_table(A, atab, cv.d2);
   // [s]B - [k]A: the A digits negated
   int8_t ds[64], dk[64];
   sc_digits16(s, ds);
@@ -587,7 +584,7 @@ int verify_strict_one(const uint8_t* msg, size_t msg_len, const uint8_t* pk, con
   for (int i = 63; i >= 0; i--) {
     if (i != 63)
       for (int j = 0; j < 4; j++) q = pt_double(q);
-    add_digit(q, g_base_tab, ds[i]);
+    add_digit(q, cv.base_tab, ds[i]);
     add_digit(q, atab, -dk[i]);
   }
   return pt_same(q, R) ? 0 : 1;
@@ -595,15 +592,15 @@ int verify_strict_one(const uint8_t* msg, size_t msg_len, const uint8_t* pk, con
 
 // ed25519-dalek 1.0.1 verify_batch over one message: 0 Ok / 1 Err; zs: 16
 // little-endian bytes per signature
-int verify_batch_one(const uint8_t* msg, size_t msg_len, const uint8_t* pks, const uint8_t* sigs, size_t n,
-                     const uint8_t* zs) {
+int verify_batch_one(const Curve& cv, const uint8_t* msg, size_t msg_len, const uint8_t* pks, const uint8_t* sigs,
+                     size_t n, const uint8_t* zs) {
   std::vector<Cached> tabs((2 * n) * 8);
   std::vector<const Cached*> tp;
   std::vector<Sc> sc;
   tp.reserve(2 * n + 1);
   sc.reserve(2 * n + 1);
   Sc bsum{{0, 0, 0, 0}};
-  tp.push_back(g_base_tab);
+  tp.push_back(cv.base_tab);
   sc.push_back(bsum);  // the B coefficient, set below
   for (size_t i = 0; i < n; i++) {
     const uint8_t* sig = sigs + 64 * i;
@@ -611,12 +608,12 @@ int verify_batch_one(const uint8_t* msg, size_t msg_len, const uint8_t* pks, con
     Sc s;
     if (!scalar_canonical(sig + 32, s)) return 1;
     Pt A, R;
-    if (!pt_decompress(pk, A) || !pt_decompress(sig, R)) return 1;
+    if (!pt_decompress(pk, cv.d, cv.sqrtm1, A) || !pt_decompress(sig, cv.d, cv.sqrtm1, R)) return 1;
     Sc z{{0, 0, 0, 0}};
     load_words(z.w, zs + 16 * i, 2);
     bsum = sc_add(bsum, sc_mul(z, s));
-    pt_table(R, &tabs[(2 * i) * 8]);
-    pt_table(A, &tabs[(2 * i + 1) * 8]);
+    pt_table(R, &tabs[(2 * i) * 8], cv.d2);
+    pt_table(A, &tabs[(2 * i + 1) * 8], cv.d2);
     tp.push_back(&tabs[(2 * i) * 8]);
     sc.push_back(z);
     tp.push_back(&tabs[(2 * i + 1) * 8]);
@@ -681,21 +678,41 @@ struct CertView {
   const uint64_t *hoff, *rounds, *voff;
 };
 
-// COA_CERT_* bits of one certificate (the engine's status semantics)
-uint8_t certificate_bits(const CertView& c, size_t i, const uint8_t* zs_all) {
-  uint8_t bits = 0, h[64], m[72];
-  sha512(c.hdata + c.hoff[i], (size_t)(c.hoff[i + 1] - c.hoff[i]), h);
-  if (std::memcmp(h, c.ids + 32 * i, 32) != 0) bits |= COA_CERT_BAD_HEADER_ID;
-  if (verify_strict_one(c.ids + 32 * i, 32, c.origins + 32 * i, c.hsigs + 64 * i)) bits |= COA_CERT_BAD_HEADER_SIG;
-  // Certificate::digest = SHA-512(id || round LE || origin)[..32] (messages.rs:226-234)
-  std::memcpy(m, c.ids + 32 * i, 32);
-  for (int b = 0; b < 8; b++) m[32 + b] = (uint8_t)(c.rounds[i] >> (8 * b));
-  std::memcpy(m + 40, c.origins + 32 * i, 32);
+// Certificate::digest and Vote::digest: SHA-512(id || round LE || origin),
+// of which the first 32 bytes count (messages.rs:226-234, 139-153)
+void round_digest(const uint8_t* id, uint64_t round, const uint8_t* origin, uint8_t h[64]) {
+  uint8_t m[72];
+  std::memcpy(m, id, 32);
+  for (int b = 0; b < 8; b++) m[32 + b] = (uint8_t)(round >> (8 * b));
+  std::memcpy(m + 40, origin, 32);
   sha512(m, 72, h);
+}
+
+// Header::verify crypto (primary/src/messages.rs:49-51,64-66): the digest
+// check and verify_strict(header.id, author), as COA_CERT_* bits
+uint8_t header_bits(const Curve& cv, const uint8_t* data, const uint64_t* off, const uint8_t* id,
+                    const uint8_t* author, const uint8_t* sig) {
+  uint8_t bits = 0, h[64];
+  sha512(data + off[0], (size_t)(off[1] - off[0]), h);
+  if (std::memcmp(h, id, 32) != 0) bits |= COA_CERT_BAD_HEADER_ID;
+  if (verify_strict_one(cv, id, 32, author, sig)) bits |= COA_CERT_BAD_HEADER_SIG;
+  return bits;
+}
+
+// COA_CERT_* bits of one certificate (the engine's status semantics)
+uint8_t certificate_bits(const Curve& cv, const CertView& c, size_t i, const uint8_t* zs_all) {
+  uint8_t bits = header_bits(cv, c.hdata, c.hoff + i, c.ids + 32 * i, c.origins + 32 * i, c.hsigs + 64 * i), h[64];
+  round_digest(c.ids + 32 * i, c.rounds[i], c.origins + 32 * i, h);
   const uint64_t v0 = c.voff[i], nv = c.voff[i + 1] - v0;
-  if (verify_batch_one(h, 32, c.vpks + 32 * v0, c.vsigs + 64 * v0, (size_t)nv, zs_all + 16 * v0))
+  if (verify_batch_one(cv, h, 32, c.vpks + 32 * v0, c.vsigs + 64 * v0, (size_t)nv, zs_all + 16 * v0))
     bits |= COA_CERT_BAD_VOTES;
   return bits;
+}
+
+bool committee_table(const uint8_t* pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                     const uint64_t* worker_offsets, size_t n_authorities, CoaProtTable& t) {
+  std::string err;
+  return coa_prot_build(pks, stakes, worker_ids, worker_offsets, n_authorities, t, err);
 }
 
 }  // namespace
@@ -704,18 +721,17 @@ extern "C" {
 
 int coa_cpu_ed25519_verify_strict(const uint8_t* msg, size_t msg_len, const uint8_t pk[32], const uint8_t sig[64]) {
   if ((!msg && msg_len) || !pk || !sig) return COA_EINVAL;
-  ensure_consts();
-  return verify_strict_one(msg, msg_len, pk, sig);
+  return verify_strict_one(curve(), msg, msg_len, pk, sig);
 }
 
 int coa_cpu_ed25519_verify_strict_many(const uint8_t* msgs, size_t msg_len, const uint8_t* pks, const uint8_t* sigs,
                                        size_t n, uint8_t* verdicts_out, int nthreads) {
   if (n == 0) return COA_OK;
   if ((!msgs && msg_len) || !pks || !sigs || !verdicts_out) return COA_EINVAL;
-  ensure_consts();
+  const Curve& cv = curve();
   parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++)
-      verdicts_out[i] = (uint8_t)verify_strict_one(msgs + i * msg_len, msg_len, pks + 32 * i, sigs + 64 * i);
+      verdicts_out[i] = (uint8_t)verify_strict_one(cv, msgs + i * msg_len, msg_len, pks + 32 * i, sigs + 64 * i);
   });
   return COA_OK;
 }
@@ -726,15 +742,14 @@ int coa_cpu_ed25519_verify_batch_groups_z(const uint8_t* msgs, const uint8_t* pk
   if (n_groups == 0) return COA_OK;
   if (!msgs || !group_offsets || !group_verdicts_out || group_offsets[0] != 0) return COA_EINVAL;
   const uint64_t total = group_offsets[n_groups];
-  for (size_t g = 0; g < n_groups; g++)
-    if (group_offsets[g + 1] < group_offsets[g]) return COA_EINVAL;
+  if (!offsets_monotone(group_offsets, n_groups)) return COA_EINVAL;
   if (total && (!pks || !sigs || !zs)) return COA_EINVAL;
-  ensure_consts();
+  const Curve& cv = curve();
   parallel_ranges(n_groups, nthreads, [&](size_t lo, size_t hi) {
     for (size_t g = lo; g < hi; g++) {
       const uint64_t a = group_offsets[g], b = group_offsets[g + 1];
       group_verdicts_out[g] =
-          (uint8_t)verify_batch_one(msgs + 32 * g, 32, pks + 32 * a, sigs + 64 * a, (size_t)(b - a), zs + 16 * a);
+          (uint8_t)verify_batch_one(cv, msgs + 32 * g, 32, pks + 32 * a, sigs + 64 * a, (size_t)(b - a), zs + 16 * a);
     }
   });
   return COA_OK;
@@ -754,8 +769,7 @@ int coa_cpu_ed25519_verify_batch(const uint8_t msg[32], const uint8_t* pks, cons
 int coa_cpu_sha512_many(const uint8_t* data, const uint64_t* offsets, size_t n, uint8_t* out64, int nthreads) {
   if (n == 0) return COA_OK;
   if (!offsets || !out64 || (!data && offsets[n] > offsets[0])) return COA_EINVAL;
-  for (size_t i = 0; i < n; i++)
-    if (offsets[i + 1] < offsets[i]) return COA_EINVAL;
+  if (!offsets_monotone(offsets, n)) return COA_EINVAL;
   parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) sha512(data + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), out64 + 64 * i);
   });
@@ -770,14 +784,13 @@ int coa_cpu_certificate_verify_many_z(const uint8_t* header_data, const uint64_t
   if (!header_offsets || !ids || !origins || !header_sigs || !rounds || !vote_offsets || !status_out ||
       vote_offsets[0] != 0)
     return COA_EINVAL;
-  for (size_t i = 0; i < n; i++)
-    if (header_offsets[i + 1] < header_offsets[i] || vote_offsets[i + 1] < vote_offsets[i]) return COA_EINVAL;
+  if (!offsets_monotone(header_offsets, n) || !offsets_monotone(vote_offsets, n)) return COA_EINVAL;
   if (header_offsets[n] > header_offsets[0] && !header_data) return COA_EINVAL;
   if (vote_offsets[n] && (!vote_pks || !vote_sigs || !zs)) return COA_EINVAL;
-  ensure_consts();
+  const Curve& cv = curve();
   const CertView c{header_data, ids, origins, header_sigs, vote_pks, vote_sigs, header_offsets, rounds, vote_offsets};
   parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) status_out[i] = certificate_bits(c, i, zs);
+    for (size_t i = lo; i < hi; i++) status_out[i] = certificate_bits(cv, c, i, zs);
   });
   return COA_OK;
 }
@@ -794,44 +807,33 @@ int coa_cpu_certificate_verify_many(const uint8_t* header_data, const uint64_t* 
                                            vote_sigs, vote_offsets, n, zs.data(), status_out, nthreads);
 }
 
-// Header::verify crypto (primary/src/messages.rs:49-51,64-66): the digest
-// check and verify_strict(header.id, author)
 int coa_cpu_header_verify_many(const uint8_t* header_data, const uint64_t* header_offsets, const uint8_t* ids,
                                const uint8_t* authors, const uint8_t* sigs, size_t n, uint8_t* status_out,
                                int nthreads) {
   if (n == 0) return COA_OK;
   if (!header_offsets || !ids || !authors || !sigs || !status_out) return COA_EINVAL;
-  for (size_t i = 0; i < n; i++)
-    if (header_offsets[i + 1] < header_offsets[i]) return COA_EINVAL;
+  if (!offsets_monotone(header_offsets, n)) return COA_EINVAL;
   if (header_offsets[n] > header_offsets[0] && !header_data) return COA_EINVAL;
-  ensure_consts();
+  const Curve& cv = curve();
   parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi; i++) {
-      uint8_t bits = 0, h[64];
-      sha512(header_data + header_offsets[i], (size_t)(header_offsets[i + 1] - header_offsets[i]), h);
-      if (std::memcmp(h, ids + 32 * i, 32) != 0) bits |= COA_CERT_BAD_HEADER_ID;
-      if (verify_strict_one(ids + 32 * i, 32, authors + 32 * i, sigs + 64 * i)) bits |= COA_CERT_BAD_HEADER_SIG;
-      status_out[i] = bits;
-    }
+    for (size_t i = lo; i < hi; i++)
+      status_out[i] = header_bits(cv, header_data, header_offsets + i, ids + 32 * i, authors + 32 * i, sigs + 64 * i);
   });
   return COA_OK;
 }
 
 // Vote::verify crypto (primary/src/messages.rs:139-153): verify_strict of
-// Vote::digest = SHA-512(id || round LE || origin)[..32] under vote.author
+// Vote::digest (round_digest) under vote.author
 int coa_cpu_vote_verify_many(const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, const uint8_t* authors,
                              const uint8_t* sigs, size_t n, uint8_t* verdicts_out, int nthreads) {
   if (n == 0) return COA_OK;
   if (!ids || !rounds || !origins || !authors || !sigs || !verdicts_out) return COA_EINVAL;
-  ensure_consts();
+  const Curve& cv = curve();
   parallel_ranges(n, nthreads, [&](size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; i++) {
-      uint8_t m[72], h[64];
-      std::memcpy(m, ids + 32 * i, 32);
-      for (int b = 0; b < 8; b++) m[32 + b] = (uint8_t)(rounds[i] >> (8 * b));
-      std::memcpy(m + 40, origins + 32 * i, 32);
-      sha512(m, 72, h);
-      verdicts_out[i] = (uint8_t)verify_strict_one(h, 32, authors + 32 * i, sigs + 64 * i);
+      uint8_t h[64];
+      round_digest(ids + 32 * i, rounds[i], origins + 32 * i, h);
+      verdicts_out[i] = (uint8_t)verify_strict_one(cv, h, 32, authors + 32 * i, sigs + 64 * i);
     }
   });
   return COA_OK;
@@ -849,14 +851,12 @@ int coa_cpu_certificate_verdict_from_status(const uint8_t* header_data, const ui
                                             const uint32_t* worker_ids, const uint64_t* worker_offsets,
                                             size_t n_authorities, uint32_t* verdicts_out, int nthreads) {
   CoaProtTable t;
-  std::string err;
-  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (!committee_table(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t)) return COA_EINVAL;
   if (n == 0) return COA_OK;
   if (!header_offsets || !ids || !origins || !rounds || !vote_offsets || !payload_counts || !status || !verdicts_out ||
       vote_offsets[0] != 0)
     return COA_EINVAL;
-  for (size_t i = 0; i < n; i++)
-    if (header_offsets[i + 1] < header_offsets[i] || vote_offsets[i + 1] < vote_offsets[i]) return COA_EINVAL;
+  if (!offsets_monotone(header_offsets, n) || !offsets_monotone(vote_offsets, n)) return COA_EINVAL;
   if (header_offsets[n] > header_offsets[0] && !header_data) return COA_EINVAL;
   if (vote_offsets[n] && !vote_pks) return COA_EINVAL;
   if (!coa_prot_counts_fit(header_offsets, payload_counts, n)) return COA_EINVAL;
@@ -895,8 +895,7 @@ int coa_cpu_header_verdict_many(const uint8_t* header_data, const uint64_t* head
                                 const uint64_t* worker_offsets, size_t n_authorities, uint32_t* verdicts_out,
                                 int nthreads) {
   CoaProtTable t;
-  std::string err;
-  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (!committee_table(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t)) return COA_EINVAL;
   if (n == 0) return COA_OK;
   if (!payload_counts || !verdicts_out) return COA_EINVAL;
   std::vector<uint8_t> st(n, 0);
@@ -914,8 +913,7 @@ int coa_cpu_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const 
                               const uint32_t* stakes, const uint32_t* worker_ids, const uint64_t* worker_offsets,
                               size_t n_authorities, uint32_t* verdicts_out, int nthreads) {
   CoaProtTable t;
-  std::string err;
-  if (!coa_prot_build(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t, err)) return COA_EINVAL;
+  if (!committee_table(committee_pks, stakes, worker_ids, worker_offsets, n_authorities, t)) return COA_EINVAL;
   if (n == 0) return COA_OK;
   if (!verdicts_out) return COA_EINVAL;
   std::vector<uint8_t> st(n, 0);

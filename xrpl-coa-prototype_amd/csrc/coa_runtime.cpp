@@ -190,14 +190,16 @@ struct KeySet {
 };
 using KeySetP = std::shared_ptr<const KeySet>;
 
-// What the contexts open on one HIP device share: B's wide comb (8.9 GB,
+// What the contexts open on one HIP device share: B's wide comb (11 GiB,
 // built once per device, not once per context) and the current key-cache
 // generation.  coa_committee_register builds a new generation on `build`
 // (no context's lock, stream or buffers), swaps it in under `mu`, and frees
 // the old one once no call or queue window holds it.
 struct DevShared {
   int id = -1;
-  uint32_t* wcomb = nullptr;  // wide B comb, COA_WCOMB_POS x 2^(W-1) entries (8.9 GB at W = 24)
+  // wide B comb: COA_WCOMB_ENTRIES = 11 x 2^23 entries of COA_WC_STRIDE = 32
+  // dwords (128 B) at W = 24: 11 GiB = 11.8 GB
+  uint32_t* wcomb = nullptr;
   hipStream_t build = nullptr;
   std::mutex mu;  // guards `keys`
   KeySetP keys;   // never null while the device is open
@@ -405,7 +407,7 @@ double key_wcomb20_budget() {
 }
 // Bytes of HBM the wide key combs of ALL key-cache generations resident on
 // one device at once may take (COA_KEY_RESIDENT_MB, default 224 GiB of the
-// MI355X's 288 GB, beside B's 8.9 GB comb and the contexts' workspaces): the
+// MI355X's 288 GB, beside B's 11.8 GB comb and the contexts' workspaces): the
 // current generation, the one a registration builds beside it, and the
 // spare kept for the next registration.  A new generation takes wide combs
 // only when they fit beside the current one; a spare is kept only when it
@@ -482,10 +484,12 @@ void reap_trailing(DevShared& sh) {
 // A device-pointer call that read generation `ks` in kernels it enqueued on
 // `s` and returns before they complete: `ks` stays held until they have (an
 // event on `s`).  Windows of the aggregation queue pin their generation until
-// complete() and need none.  If no event can be recorded, the call waits for
-// its stream instead.
+// complete() and need none: a call that read the pinned generation itself
+// returns at once.  A pin for another device does not cover `ks` (keys_now
+// then handed out this device's current generation), so that call trails.
+// If no event can be recorded, the call waits for its stream instead.
 int trail_keys(Dev& d, const KeySetP& ks, hipStream_t s) {
-  if (t_keys_pinned && *t_keys_pinned) return COA_OK;
+  if (t_keys_pinned && ks == *t_keys_pinned) return COA_OK;
   DevShared& sh = *d.sh;
   reap_trailing(sh);
   hipEvent_t ev = nullptr;
