@@ -109,6 +109,57 @@ def test_split_path_ragged_small_calls(engine, n, monkeypatch):
     assert (got == exp).all(), np.nonzero(got != exp)[0][:10]
 
 
+def _ragged_forced(engine, n, env, monkeypatch):
+    """test_split_path_ragged_small_calls's check with the switches of env set."""
+    from workloads import adversarial_mix, messages
+
+    monkeypatch.setenv("COA_LAT_MAX", "0")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    m0 = messages(n, 31)
+    pks, sigs = engine.sign_many(np.frombuffer(bytes(range(256)) * ((32 * n) // 256 + 1), np.uint8)[: 32 * n]
+                                 .reshape(n, 32), m0)
+    msgs, pks, sigs, cls = adversarial_mix(m0, pks, sigs, frac=0.3, seed=n, mixed_pool=_pool())
+    got = engine.verify_strict_many(msgs, pks, sigs)
+    exp = co.verify_strict_many(msgs, pks, sigs, 1)
+    assert (got == exp).all(), np.nonzero(got != exp)[0][:10]
+    if n >= 64:
+        assert set(np.unique(cls[cls >= 0])) == set(range(8))
+
+
+@pytest.mark.parametrize("n", [1, 65, 257])
+@pytest.mark.parametrize("wcomb", [None, "0"])
+@pytest.mark.parametrize("split_eb", [None, "0"])
+@pytest.mark.parametrize("il", ["0", "1"])
+def test_one_lane_main_kernel_ragged(engine, il, split_eb, wcomb, n, monkeypatch):
+    """k_verify_main forced plain and interleaved (COA_MAIN_IL), with [e]B
+    from phase 1 or in the main kernel (COA_SPLIT_EB), from the wide or the
+    narrow comb (COA_WCOMB), on one lane, a wave and a lane, a block and a
+    lane."""
+    env = {"COA_MAIN_IL": il}
+    if split_eb is not None:
+        env["COA_SPLIT_EB"] = split_eb
+    if wcomb is not None:
+        env["COA_WCOMB"] = wcomb
+    _ragged_forced(engine, n, env, monkeypatch)
+
+
+@pytest.mark.parametrize("n", [63, 64, 65])
+def test_two_wave_main_kernel_ragged(engine, n, monkeypatch):
+    """k_verify_main2 forced (COA_MAIN_TWO=1) around its workgroup's 64 items."""
+    _ragged_forced(engine, n, {"COA_MAIN_TWO": "1"}, monkeypatch)
+
+
+@pytest.mark.parametrize("n", [1, 65, 257])
+@pytest.mark.parametrize("wcomb", [None, "0"])
+def test_one_kernel_path_ragged(engine, wcomb, n, monkeypatch):
+    """k_halve + k_verify_halved (COA_VERIFY_SPLIT=0), wide and narrow comb."""
+    env = {"COA_VERIFY_SPLIT": "0"}
+    if wcomb is not None:
+        env["COA_WCOMB"] = wcomb
+    _ragged_forced(engine, n, env, monkeypatch)
+
+
 def test_adversarial_mix_streamed_through_the_queue(engine):
     """The C2-size adversarial mix (65,536 triples, 1 % over the 8 classes)
     submitted one signature per request through the aggregation queue from a

@@ -5,12 +5,23 @@ blocks assembled into `.subsection 1` are left out): the outermost loop of the
 kernel is the digit loop, the loop nested in it the three-pass doubling loop,
 so one digit issues  body(outer) - body(inner) + 3 * body(inner)  instructions
 (the body includes the conversion that every digit but the last ends with).
-Also prints the straight-line hot-path count of k_pre_halve<3> and the VGPR /
-spill figures of every kernel in the file's metadata.
+k_verify_main_sums has one digit loop per role: the consumer's is the one with
+the doubling loop nested in it, the producer's the one without.
+Also prints the straight-line hot-path count of both k_pre_halve<3, *>
+instances and the register, spill, scratch and LDS figures of every kernel in
+the file's metadata.
 
-usage: python tools/digit_count.py [coa_halved.s]
-       (without an argument the file is compiled here with build.py's flags)"""
+--json FILE writes, per kernel symbol, those figures, the hot-path instruction
+count and a SHA-256 of the hot-path instruction text (labels, comments and
+directives stripped, block labels renumbered per function), so two builds are
+compared by diffing two small files.
+
+usage: python tools/digit_count.py [--json FILE] [coa_halved.s]
+       (without a .s argument the file is compiled here with build.py's flags)"""
+import argparse
 import collections
+import hashlib
+import json
 import os
 import re
 import subprocess
@@ -21,8 +32,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "xrpl-coa-prototype_amd"))
 
 MAIN = "_Z13k_verify_mainILi1ELb1EEv"
-PRE = "_Z11k_pre_halveILi3EEv"
+SUMS = "_Z18k_verify_main_sumsILi0ELb0EEv"
+PRE = "_Z11k_pre_halveILi3E"
 WATCH = ("v_mad_u64_u32", "v_addc_co_u32", "v_mov_b32", "v_cndmask_b32", "s_nop")
+KEYS = ["all"] + list(WATCH)
+META = ("vgpr_count", "vgpr_spill_count", "sgpr_count", "sgpr_spill_count", "private_segment_fixed_size",
+        "group_segment_fixed_size")
 
 
 def compile_s(src, extra=()):
@@ -87,45 +102,103 @@ def tally(lines, lo, hi):
     return c
 
 
+def inner_of(ls, outer):
+    """The longest loop strictly inside outer (not outer's other back edges), or None."""
+    inner = [r for r in ls if outer[0] < r[0] and r[1] <= outer[1]]
+    return max(inner, key=lambda r: r[1] - r[0]) if inner else None
+
+
 def digit(text):
     lines = function_lines(text, MAIN)
     ls = loops(lines)
     outer = ls[0]
-    inner = [r for r in ls[1:] if outer[0] < r[0] and r[1] <= outer[1]]  # not the digit loop's other back edge
-    inner = max(inner, key=lambda r: r[1] - r[0])
+    inner = inner_of(ls[1:], outer)
     o, i = tally(lines, *outer), tally(lines, *inner)
-    return {k: o[k] + 2 * i[k] for k in ["all"] + list(WATCH)}, i
+    return {k: o[k] + 2 * i[k] for k in KEYS}, {k: i[k] for k in KEYS}
+
+
+def sums_digit(text):
+    """(consumer per digit, its doubling pass, producer per digit) of k_verify_main_sums."""
+    lines = function_lines(text, SUMS)
+    ls = loops(lines)
+    top = [r for r in ls if not any(o != r and o[0] <= r[0] and r[1] <= o[1] for o in ls)]
+    cons = [r for r in top if inner_of(ls, r)]
+    prod = [r for r in top if not inner_of(ls, r)]
+    if len(cons) != 1 or len(prod) != 1:
+        return None
+    inner = inner_of(ls, cons[0])
+    o, i, p = tally(lines, *cons[0]), tally(lines, *inner), tally(lines, *prod[0])
+    return {k: o[k] + 2 * i[k] for k in KEYS}, {k: i[k] for k in KEYS}, {k: p[k] for k in KEYS}
 
 
 def metadata(text):
-    out, name = [], None
+    """{kernel symbol: {figure: value}} from the amdhsa.kernels metadata (keys in alphabetical order)."""
+    out, cur = {}, {}
     for line in text.splitlines():
-        m = re.match(r"\s+\.name:\s+(_Z\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.match(r"\s+\.vgpr_count:\s+(\d+)", line)
-        if m:
-            v = int(m.group(1))
-        m = re.match(r"\s+\.vgpr_spill_count:\s+(\d+)", line)
-        if m and name:
-            out.append((name, v, int(m.group(1))))
-            name = None
+        m = re.match(r"\s+(?:- )?\.(\w+):\s+(\S+)", line)
+        if not m:
+            continue
+        key, val = m.groups()
+        if key == "name" and val.startswith("_Z"):
+            cur["name"] = val
+        elif key in META:
+            cur[key] = int(val)
+        if key == "vgpr_spill_count":
+            if "name" in cur:
+                out[cur.pop("name")] = cur
+            cur = {}
     return out
 
 
+def digest(lines):
+    """(instruction count, SHA-256) of a function's hot-path instruction text."""
+    h, n = hashlib.sha256(), 0
+    for _, op, s in lines:
+        if op:
+            h.update((re.sub(r"\.LBB\d+_", ".LBB_", " ".join(s.split())) + "\n").encode())
+            n += 1
+    return n, h.hexdigest()
+
+
+def fmt(c):
+    return " ".join(f"{k}={c[k]}" for k in KEYS)
+
+
 def main():
-    path = sys.argv[1] if len(sys.argv) > 1 else compile_s("coa_halved.hip")
-    text = open(path).read()
-    if MAIN in text:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", metavar="FILE")
+    ap.add_argument("asm", nargs="?")
+    a = ap.parse_args()
+    text = open(a.asm or compile_s("coa_halved.hip")).read()
+    meta = metadata(text)
+    report = {}
+    for name, m in meta.items():
+        n, h = digest(function_lines(text, name + ":"))
+        report[name] = dict(m, hot_instructions=n, hot_sha256=h)
+    main_k = next((k for k in meta if k.startswith(MAIN)), None)
+    sums_k = next((k for k in meta if k.startswith(SUMS)), None)
+    if main_k:
         d, inner = digit(text)
-        print("k_verify_main<1,true> per digit:", " ".join(f"{k}={v}" for k, v in d.items()))
-        print("  one doubling pass:", " ".join(f"{k}={inner[k]}" for k in ["all"] + list(WATCH)))
-    if PRE in text:
-        lines = function_lines(text, PRE)
-        t = tally(lines, 0, len(lines) - 1)
-        print("k_pre_halve<3> hot-path text:", " ".join(f"{k}={t[k]}" for k in ["all"] + list(WATCH)))
-    for name, v, s in metadata(text):
-        print(f"  {name[:60]:60s} vgpr {v:4d} spill {s}")
+        print("k_verify_main<1,true> per digit:", fmt(d))
+        print("  one doubling pass:", fmt(inner))
+        report[main_k].update(per_digit=d, doubling_pass=inner)
+    sd = sums_digit(text) if sums_k else None
+    if sd:
+        print("k_verify_main_sums<0,false> consumer per digit:", fmt(sd[0]))
+        print("  one doubling pass:", fmt(sd[1]))
+        print("k_verify_main_sums<0,false> producer per digit:", fmt(sd[2]))
+        report[sums_k].update(consumer_per_digit=sd[0], doubling_pass=sd[1], producer_per_digit=sd[2])
+    for name in meta:
+        if name.startswith(PRE):
+            lines = function_lines(text, name + ":")
+            print(f"{name[:name.index('Ev') + 2]} hot-path text:", fmt(tally(lines, 0, len(lines) - 1)))
+    for name, m in meta.items():
+        print(f"  {name[:44]:44s} vgpr {m['vgpr_count']:4d} spill {m['vgpr_spill_count']:3d} sgpr {m['sgpr_count']:3d}"
+              f" private {m['private_segment_fixed_size']:4d} lds {m['group_segment_fixed_size']}")
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(report, f, indent=1, sort_keys=True)
+            f.write("\n")
 
 
 if __name__ == "__main__":

@@ -18,10 +18,20 @@
 //
 // Kernels:
 //   k_build_comb     comb table: entry (j, v) = (v+1)*256^j*B, affine Niels
+//   k_build_wcomb, k_check_wcomb
+//                    the wide comb of B from the narrow one, and its check
 //   k_halve          (k, s) -> (c, |d|, e, H, sign d)
 //   k_verify_halved  decompression + small-order checks + Q == O
-//   k_pre_halve, k_verify_main / k_verify_main2 / k_verify_main_sums
-//                    the same in two launches (the default path)
+//   k_pre_halve      phase 1 of the same in two launches (the default path)
+//   k_verify_main<3, false> / <1, true>, k_verify_main2, k_verify_main_sums
+//                    phase 2: one of the four, chosen by coa_pick_main
+//                    (coa_main_pick.h, host-only) from size and COA_MAIN_*
+// The steps of k_verify_main and k_verify_halved -- the Horner digit step,
+// the digit extraction, the [e]B comb sums, a cached point as 32 dwords, the
+// verdict -- and the comb builders' two ends stand in coa_halved_dev.h.
+// k_pre_halve's [e]B tail, k_verify_main2 and k_verify_main_sums keep these
+// steps written out: their code generation, and with it their speed, changes
+// with the helpers.
 #include "coa_halved.h"
 
 #include <atomic>
@@ -32,20 +42,13 @@
 #include "coa_ge.h"
 #include "coa_ge_sums.h"
 #include "coa_halve.h"
+#include "coa_halved_dev.h"
+#include "coa_main_pick.h"
 #include "coa_sc.h"
 #include "coa_sha512.h"
 #include "coa_smul.h"
 
-namespace {
 using namespace coa_halve;
-
-COA_DEV int wave_max(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_build_comb(uint32_t* __restrict__ comb, const uint32_t* __restrict__ btab_g) {
@@ -53,32 +56,12 @@ __global__ void __launch_bounds__(256) k_build_comb(uint32_t* __restrict__ comb,
   lds_load_btable(btab, btab_g);
   const int id = blockIdx.x * blockDim.x + threadIdx.x;  // 0 .. 4095
   const int j = id >> 7, v = id & 127;
-  uint32_t wide[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) wide[i] = 0;
-  // (v + 1) << (8 j) as a 512-bit value, reduced mod l
-  const int bitpos = 8 * j;
-  const uint64_t m = (uint64_t)(v + 1) << (bitpos & 31);
-  for (int i = 0; i < 16; i++) {
-    if (i == (bitpos >> 5)) wide[i] = (uint32_t)m;
-    if (i == (bitpos >> 5) + 1) wide[i] = (uint32_t)(m >> 32);
-  }
   sc x;
-  sc_reduce512(x, wide);
+  sc_small_shifted(x, (uint32_t)(v + 1), 8 * j);  // (v + 1) * 256^j mod l
   ge_p2 P;
   fixed_base_mul(P, x.v, btab);
-  fe zi, xx, yy, xy, d2, n0, n1, n2;
-  fe_invert(zi, P.Z);
-  fe_mul(xx, P.X, zi);
-  fe_mul(yy, P.Y, zi);
-  fe_mul(xy, xx, yy);
-  fe_const_d2(d2);
-  fe_add(n0, yy, xx);
-  fe_sub(n1, yy, xx);
-  fe_mul(n2, xy, d2);
-  fe_canon(n0, n0);
-  fe_canon(n1, n1);
-  fe_canon(n2, n2);
+  fe n0, n1, n2;
+  affine_niels_canon(n0, n1, n2, P.X, P.Y, P.Z);
   uint32_t* e = comb + (uint64_t)id * 24;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -95,51 +78,21 @@ __global__ void __launch_bounds__(256) k_build_wcomb(uint32_t* __restrict__ wcom
   if (id >= COA_WCOMB_ENTRIES) return;
   const int j = (int)(id / COA_WCOMB_MAG);
   const uint32_t m = (uint32_t)(id % COA_WCOMB_MAG) + 1;
-  uint32_t wide[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) wide[i] = 0;
-  const int bitpos = COA_WCOMB_W * j;
-  const uint64_t mm = (uint64_t)m << (bitpos & 31);
-  for (int i = 0; i < 16; i++) {
-    if (i == (bitpos >> 5)) wide[i] = (uint32_t)mm;
-    if (i == (bitpos >> 5) + 1) wide[i] = (uint32_t)(mm >> 32);
-  }
   sc x;
-  sc_reduce512(x, wide);
+  sc_small_shifted(x, m, COA_WCOMB_W * j);
   uint32_t e[8];
 #pragma unroll
   for (int i = 0; i < 8; i++) e[i] = x.v[i];
-  add_const_word(e, 0x80808080u);
   ge_p3 acc3;
-  ge_p1p1 t;
   ge_p3_identity(acc3);
-#pragma unroll 1
-  for (int k = 0; k < 32; k++) {
-    const int ek = (int)take_low_byte(e) - 128;
-    ge_niels qb;
-    comb_select(qb, comb, k, ek);
-    ge_madd(t, acc3, qb);
-    ge_p1p1_to_p3(acc3, t);
-  }
-  fe zi, xx, yy, xy, d2, n0, n1, n2;
-  fe_invert(zi, acc3.Z);
-  fe_mul(xx, acc3.X, zi);
-  fe_mul(yy, acc3.Y, zi);
-  fe_mul(xy, xx, yy);
-  fe_const_d2(d2);
-  fe_add(n0, yy, xx);
-  fe_sub(n1, yy, xx);
-  fe_mul(n2, xy, d2);
-  fe_canon(n0, n0);
-  fe_canon(n1, n1);
-  fe_canon(n2, n2);
-  uint4* o = reinterpret_cast<uint4*>(wcomb + id * COA_WC_STRIDE);
-  o[0] = make_uint4(n0.v[0], n0.v[1], n0.v[2], n0.v[3]);
-  o[1] = make_uint4(n0.v[4], n0.v[5], n0.v[6], n0.v[7]);
-  o[2] = make_uint4(n1.v[0], n1.v[1], n1.v[2], n1.v[3]);
-  o[3] = make_uint4(n1.v[4], n1.v[5], n1.v[6], n1.v[7]);
-  o[4] = make_uint4(n2.v[0], n2.v[1], n2.v[2], n2.v[3]);
-  o[5] = make_uint4(n2.v[4], n2.v[5], n2.v[6], n2.v[7]);
+  ge_p1p1 t;
+  comb_accumulate(acc3, t, e, comb);
+  fe n0, n1, n2;
+  affine_niels_canon(n0, n1, n2, acc3.X, acc3.Y, acc3.Z);
+  uint32_t* o = wcomb + id * COA_WC_STRIDE;
+  store8_u4(o, n0.v);
+  store8_u4(o + 8, n1.v);
+  store8_u4(o + 16, n2.v);
 }
 
 namespace {
@@ -250,14 +203,11 @@ COA_DEV void halve_rec(uint32_t* k, const uint32_t* s, uint32_t i, uint32_t* __r
   // c + 0x88..8 minus 8 is digit p, and every digit at p >= H is 0
   add_const_word(c, 0x88888888u);
   add_const_word(d, 0x88888888u);
-  uint4* o = reinterpret_cast<uint4*>(rec + (uint64_t)i * 32);
-  o[0] = make_uint4(c[0], c[1], c[2], c[3]);
-  o[1] = make_uint4(c[4], c[5], c[6], c[7]);
-  o[2] = make_uint4(d[0], d[1], d[2], d[3]);
-  o[3] = make_uint4(d[4], d[5], d[6], d[7]);
-  o[4] = make_uint4(e.v[0], e.v[1], e.v[2], e.v[3]);
-  o[5] = make_uint4(e.v[4], e.v[5], e.v[6], e.v[7]);
-  o[6] = make_uint4((uint32_t)H | (neg ? 0x80000000u : 0u), 0, 0, 0);
+  uint32_t* o = rec + (uint64_t)i * 32;
+  store8_u4(o, c);
+  store8_u4(o + 8, d);
+  store8_u4(o + 16, e.v);
+  *reinterpret_cast<uint4*>(o + 24) = make_uint4((uint32_t)H | (neg ? 0x80000000u : 0u), 0, 0, 0);
 #pragma unroll
   for (int j = 0; j < 8; j++) e_out[j] = e.v[j];
 }
@@ -266,23 +216,9 @@ COA_DEV void halve_rec(uint32_t* k, const uint32_t* s, uint32_t i, uint32_t* __r
 COA_DEV void halve_one(const uint32_t* __restrict__ kbuf, const uint8_t* __restrict__ sigs, uint32_t i,
                        uint32_t* __restrict__ rec) {
   uint32_t k[8], s[8], e[8];
-  const uint4* kq = reinterpret_cast<const uint4*>(kbuf + (uint64_t)i * 8);
-  const uint4* sq = reinterpret_cast<const uint4*>(sigs + (uint64_t)i * 64 + 32);
-  uint4 v0 = kq[0], v1 = kq[1];
-  k[0] = v0.x; k[1] = v0.y; k[2] = v0.z; k[3] = v0.w;
-  k[4] = v1.x; k[5] = v1.y; k[6] = v1.z; k[7] = v1.w;
-  v0 = sq[0];
-  v1 = sq[1];
-  s[0] = v0.x; s[1] = v0.y; s[2] = v0.z; s[3] = v0.w;
-  s[4] = v1.x; s[5] = v1.y; s[6] = v1.z; s[7] = v1.w;
+  load8_u4(k, kbuf + (uint64_t)i * 8);
+  load8_u4(s, sigs + (uint64_t)i * 64 + 32);
   halve_rec(k, s, i, rec, e);
-}
-
-COA_DEV void load8_u4(uint32_t* dst, const void* src) {
-  const uint4* q = reinterpret_cast<const uint4*>(src);
-  const uint4 a = q[0], b = q[1];
-  dst[0] = a.x; dst[1] = a.y; dst[2] = a.z; dst[3] = a.w;
-  dst[4] = b.x; dst[5] = b.y; dst[6] = b.z; dst[7] = b.w;
 }
 
 // The checks that do not need k (the "pre" roles of k_pre_halve), for one of
@@ -462,7 +398,7 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_main(const uint32_t* __re
   }
   const bool ok = live && fl == 0x0101u;
   const uint32_t meta = live ? meta0 : 0u;
-  const int H = wave_max(ok ? (int)(meta & 0xffu) : 0);
+  const int H = wave_max(ok ? (int)(meta & 0xffu) : 0);  // wave-uniform digit count
   MAIN_MARK(1)
   const bool dneg = (meta >> 31) != 0;
   uint8_t verdict = 1;
@@ -473,96 +409,37 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_main(const uint32_t* __re
     ge_p3_identity(acc3);
 #pragma unroll 1
     for (int pos = H - 1; pos >= 0; pos--) {
-      const int sh = 4 * (pos & 7);
-      const uint32_t wc = IL ? cw[pos >> 3] : myrec[pos >> 3];
-      const uint32_t wd = IL ? dw[pos >> 3] : myrec[8 + (pos >> 3)];
-      const int dc = (int)((wc >> sh) & 15u) - 8;
-      const int dd = (int)((wd >> sh) & 15u) - 8;
+      const int dc = digit_of(IL ? cw[pos >> 3] : myrec[pos >> 3], pos);
+      const int dd = digit_of(IL ? dw[pos >> 3] : myrec[8 + (pos >> 3)], pos);
       const int dr = dneg ? -dd : dd;
       ge_cached qa, qr;
       if constexpr (IL) {  // both entries in flight during the four doublings
         tab2_load(qa, scr, i, 0, dc);
         tab2_load(qr, scr, i, 1, dr);
       }
-      if (pos != H - 1) {
-#pragma unroll 1
-        for (int k = 0; k < 3; k++) {
-          if constexpr (IL) {
-            ge_p2_dbl_il(t, acc2);
-            ge_p1p1_to_p2_il(acc2, t);
-          } else {
-            ge_p2_dbl(t, acc2);
-            ge_p1p1_to_p2(acc2, t);
-          }
-        }
-        if constexpr (IL) {
-          ge_p2_dbl_il(t, acc2);
-          ge_p1p1_to_p3_il(acc3, t);
-        } else {
-          ge_p2_dbl(t, acc2);
-          ge_p1p1_to_p3(acc3, t);
-        }
-      }
-      if constexpr (IL) {
-        ge_add_il(t, acc3, qa, dc < 0);
-        ge_p1p1_to_p3_il(acc3, t);
-        ge_add_il(t, acc3, qr, dr < 0);
-        if (pos != 0) ge_p1p1_to_p2_il(acc2, t);
-      } else {
-        tab2_load(qa, scr, i, 0, dc);
-        ge_add(t, acc3, qa, dc < 0);
-        ge_p1p1_to_p3(acc3, t);
-        tab2_load(qr, scr, i, 1, dr);
-        ge_add(t, acc3, qr, dr < 0);
-        if (pos != 0) ge_p1p1_to_p2(acc2, t);
-      }
+      horner_x16<IL>(acc3, acc2, t, pos != H - 1);
+      if constexpr (!IL) tab2_load(qa, scr, i, 0, dc);
+      add<IL>(t, acc3, qa, dc < 0);
+      to_p3<IL>(acc3, t);
+      if constexpr (!IL) tab2_load(qr, scr, i, 1, dr);
+      add<IL>(t, acc3, qr, dr < 0);
+      if (pos != 0) to_p2<IL>(acc2, t);
     }
     MAIN_MARK(2)
-    if constexpr (IL)
-      ge_p1p1_to_p3_il(acc3, t);
-    else
-      ge_p1p1_to_p3(acc3, t);
+    to_p3<IL>(acc3, t);
     if (!ebp) {  // [e]B here, from the combs
       uint32_t e[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) e[j] = myrec[16 + j];
-      if (wcomb) {
-        wcomb_accumulate<IL>(acc3, e, wcomb);
-      } else {
-        add_const_word(e, 0x80808080u);
-#pragma unroll 1
-        for (int j = 0; j < 32; j++) {
-          const int ej = (int)take_low_byte(e) - 128;
-          ge_niels qb;
-          comb_select(qb, comb, j, ej);
-          ge_madd(t, acc3, qb);
-          ge_p1p1_to_p3(acc3, t);
-        }
-      }
-    } else {
-    // + [e]B, computed by the halving role
-    ge_cached eb;
-    fe* f[4] = {&eb.YplusX, &eb.YminusX, &eb.Z, &eb.T2d};
-    if constexpr (IL) {
-#pragma unroll
-      for (int q = 0; q < 4; q++)
-#pragma unroll
-        for (int k = 0; k < 8; k++) f[q]->v[k] = ebw[8 * q + k];
-    } else {
-    const uint4* src = reinterpret_cast<const uint4*>(ebp + (uint64_t)i * 32);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const uint4 v0 = src[2 * q], v1 = src[2 * q + 1];
-      f[q]->v[0] = v0.x; f[q]->v[1] = v0.y; f[q]->v[2] = v0.z; f[q]->v[3] = v0.w;
-      f[q]->v[4] = v1.x; f[q]->v[5] = v1.y; f[q]->v[6] = v1.z; f[q]->v[7] = v1.w;
+      eb_accumulate<IL>(acc3, t, e, comb, wcomb);
+    } else {  // + [e]B, computed by the halving role
+      ge_cached eb;
+      if constexpr (IL) cached_from_words(eb, ebw);
+      else cached_load(eb, ebp + (uint64_t)i * 32);
+      ge_add(t, acc3, eb);
+      ge_p1p1_to_p3(acc3, t);
     }
-    }
-    ge_add(t, acc3, eb);
-    ge_p1p1_to_p3(acc3, t);
-    }
-    ge_p2 q2;
-    ge_p3_to_p2(q2, acc3);
-    verdict = ge_p2_is_identity(q2) ? 0 : 1;
+    verdict = verdict_of(acc3);
   }
   if (live) verdicts[i] = verdict;
   MAIN_MARK(3)
@@ -822,20 +699,10 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __r
     uint32_t meta = 0;
     const uint32_t* myrec = rec + (uint64_t)(live ? i : 0) * 32;
     if (live) {
-      const uint4* p = reinterpret_cast<const uint4*>(pks + (uint64_t)i * 32);
-      const uint4* g = reinterpret_cast<const uint4*>(sigs + (uint64_t)i * 64);
-      const uint4* r = reinterpret_cast<const uint4*>(rec + (uint64_t)i * 32);
-      uint4 v;
-#define LD8(dst, src, o)                                                   \
-  v = src[o];                                                              \
-  dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;                  \
-  v = src[o + 1];                                                          \
-  dst[4] = v.x; dst[5] = v.y; dst[6] = v.z; dst[7] = v.w;
-      LD8(aw, p, 0);
-      LD8(rw, g, 0);
-      LD8(sw, g, 2);
-#undef LD8
-      meta = r[6].x;
+      load8_u4(aw, pks + (uint64_t)i * 32);
+      load8_u4(rw, sigs + (uint64_t)i * 64);
+      load8_u4(sw, sigs + (uint64_t)i * 64 + 32);
+      meta = rec[(uint64_t)i * 32 + 24];
     } else {
 #pragma unroll
       for (int j = 0; j < 8; j++) aw[j] = rw[j] = sw[j] = 0;
@@ -875,18 +742,9 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __r
       ge_p3_identity(acc3);
 #pragma unroll 1
       for (int pos = H - 1; pos >= 0; pos--) {
-        const int sh = 4 * (pos & 7);
-        const int dc = (int)((myrec[pos >> 3] >> sh) & 15u) - 8;
-        const int dd = (int)((myrec[8 + (pos >> 3)] >> sh) & 15u) - 8;
-        if (pos != H - 1) {
-#pragma unroll 1
-          for (int k = 0; k < 3; k++) {
-            ge_p2_dbl(t, acc2);
-            ge_p1p1_to_p2(acc2, t);
-          }
-          ge_p2_dbl(t, acc2);
-          ge_p1p1_to_p3(acc3, t);
-        }
+        const int dc = digit_of(myrec[pos >> 3], pos);
+        const int dd = digit_of(myrec[8 + (pos >> 3)], pos);  // the sign of d is in R's table here
+        horner_x16<false>(acc3, acc2, t, pos != H - 1);
         ge_cached q;
         tab2_load(q, scr, lane, 0, dc);
         ge_add(t, acc3, q, dc < 0);
@@ -899,24 +757,8 @@ __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __r
       uint32_t e[8];
 #pragma unroll
       for (int j = 0; j < 8; j++) e[j] = myrec[16 + j];
-      if (wcomb) {
-        // [e]B from the wide HBM comb: 13 mixed additions
-        wcomb_accumulate(acc3, e, wcomb);
-      } else {
-        // [e]B by the doubling-free radix-256 comb
-        add_const_word(e, 0x80808080u);
-#pragma unroll 1
-        for (int j = 0; j < 32; j++) {
-          const int ej = (int)take_low_byte(e) - 128;
-          ge_niels qb;
-          comb_select(qb, comb, j, ej);
-          ge_madd(t, acc3, qb);
-          ge_p1p1_to_p3(acc3, t);
-        }
-      }
-      ge_p2 q2;
-      ge_p3_to_p2(q2, acc3);
-      verdict = ge_p2_is_identity(q2) ? 0 : 1;
+      eb_accumulate<false>(acc3, t, e, comb, wcomb);
+      verdict = verdict_of(acc3);
     }
     if (live) verdicts[i] = verdict;
   }
@@ -976,47 +818,18 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   static const uint32_t pre_b = block_env("COA_PRE_BLOCK"), main_b = block_env("COA_MAIN_BLOCK");
   const uint32_t blocks = (n + pre_b - 1) / pre_b;
   const int aligned = ((msg_len & 3) == 0) && (((uintptr_t)msgs & 3) == 0);
-  // COA_PRE_PRIO=0: the hash/halving role at the default wave priority (A/B).
-  // A library compiled with -DCOA_PRE_DIAG_BUILD also reads COA_PRE_DIAG=2 / 4:
-  // skip the decompression / hash roles (role timing only, tools/pre_roles.sh;
-  // verdicts are then meaningless, so release builds cannot reach it).
-  // COA_PRE_PRIO=3: the raised priority also through the [e]B additions (bit
-  // 8; A/B).  Bits 2 and 4 are the diagnostics below.
-  static const int prio = (!getenv("COA_PRE_PRIO") ? 1
-                           : atoi(getenv("COA_PRE_PRIO")) == 0 ? 0
-                           : atoi(getenv("COA_PRE_PRIO")) == 3 ? (1 | 8) : 1)
+  // COA_PRE_PRIO / COA_PRE_DIAG: coa_pre_prio_bits (coa_main_pick.h)
 #ifdef COA_PRE_DIAG_BUILD
-                          | (getenv("COA_PRE_DIAG") ? atoi(getenv("COA_PRE_DIAG")) & 6 : 0)
+  static const int prio = coa_pre_prio_bits(getenv("COA_PRE_PRIO"), getenv("COA_PRE_DIAG"));
+#else
+  static const int prio = coa_pre_prio_bits(getenv("COA_PRE_PRIO"), nullptr);
 #endif
-      ;
-  // at most one wave per SIMD (65,536 items on the 256 CUs of an MI355X, the
-  // C2 size): the interleaved formulas; COA_MAIN_IL=0/1 forces either (A/B)
-  const char* il_env = getenv("COA_MAIN_IL");
-  const bool il = il_env ? atoi(il_env) != 0 : n <= one_wave_per_simd_items();
-  // an item's two chains in two waves (k_verify_main2) when the call has at
-  // most a quarter wave per SIMD of items: its waves then run on SIMDs the
-  // one-wave kernel leaves idle (4,096 / 16,384 items: 0.507 / 0.511 vs
-  // 0.594 / 0.602 ms per call).  At 32,768 some SIMDs already get two of its
-  // waves (0.82 vs 0.65 ms), and at C2's size the doubled doublings cost
-  // more than the second wave per SIMD wins back (0.90 vs 0.72 ms).
-  // COA_MAIN_TWO=0/1 forces either (A/B).  An explicit COA_MAIN_IL (without
-  // COA_MAIN_TWO) selects the one-lane kernel it names at every size, so an
-  // A/B of COA_MAIN_IL alone never measures k_verify_main2 instead.
-  const char* two_s = getenv("COA_MAIN_TWO");
-  const int two_env = two_s ? atoi(two_s) : (il_env ? 0 : -1);
-  // each digit's table sum in a second wave (k_verify_main_sums): above
-  // k_verify_main2's sizes and up to one wave per SIMD, where the one-lane
-  // kernel leaves half of every SIMD's issue slots idle.  COA_MAIN_SUMS=0/1
-  // forces either at every size (A/B; 1 goes before COA_MAIN_TWO); an
-  // explicit COA_MAIN_IL or COA_MAIN_TWO without it keeps selecting the
-  // kernels those name.
-  const char* sums_s = getenv("COA_MAIN_SUMS");
-  const int sums_env = sums_s ? atoi(sums_s) : ((il_env || two_s) ? 0 : -1);
-  const bool sums = ebp && (sums_env >= 0 ? sums_env != 0
-                                          : 4ull * n > one_wave_per_simd_items() && n <= one_wave_per_simd_items());
-  const bool two = ebp && !sums && (two_env >= 0 ? two_env != 0 : 4ull * n <= one_wave_per_simd_items());
+  // COA_MAIN_IL / COA_MAIN_TWO / COA_MAIN_SUMS, read per call: coa_pick_main
+  const CoaMainKernel kernel =
+      coa_pick_main(n, one_wave_per_simd_items(), ebp != nullptr, coa_env_switch(getenv("COA_MAIN_IL")),
+                    coa_env_switch(getenv("COA_MAIN_TWO")), coa_env_switch(getenv("COA_MAIN_SUMS")));
   // phase 1 stores table 1 in the form the main kernel launched below reads
-  if (sums)
+  if (kernel == COA_MAIN_SUMS)
     hipLaunchKernelGGL((k_pre_halve<3, true>), dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned,
                        kbuf, n, rec, flags, scratch, ebp, comb, wcomb, blocks, prio);
   else
@@ -1024,17 +837,24 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
                        kbuf, n, rec, flags, scratch, ebp, comb, wcomb, blocks, prio);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (sums)
-    hipLaunchKernelGGL((k_verify_main_sums<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512), 0, s,
-                       rec, flags, n, verdicts, scratch, ebp);
-  else if (two)
-    hipLaunchKernelGGL(k_verify_main2, dim3((n + 63) / 64), dim3(128), 0, s, rec, flags, n, verdicts, scratch, ebp);
-  else if (il)
-    hipLaunchKernelGGL((k_verify_main<1, true>), dim3((n + main_b - 1) / main_b), dim3(main_b), 0, s, rec, flags, n,
-                       verdicts, scratch, ebp, comb, wcomb);
-  else
-    hipLaunchKernelGGL((k_verify_main<3, false>), dim3((n + main_b - 1) / main_b), dim3(main_b), 0, s, rec, flags, n,
-                       verdicts, scratch, ebp, comb, wcomb);
+  const dim3 main_grid((n + main_b - 1) / main_b);
+  switch (kernel) {
+    case COA_MAIN_SUMS:
+      hipLaunchKernelGGL((k_verify_main_sums<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512), 0,
+                         s, rec, flags, n, verdicts, scratch, ebp);
+      break;
+    case COA_MAIN_TWO:
+      hipLaunchKernelGGL(k_verify_main2, dim3((n + 63) / 64), dim3(128), 0, s, rec, flags, n, verdicts, scratch, ebp);
+      break;
+    case COA_MAIN_IL:
+      hipLaunchKernelGGL((k_verify_main<1, true>), main_grid, dim3(main_b), 0, s, rec, flags, n, verdicts, scratch,
+                         ebp, comb, wcomb);
+      break;
+    case COA_MAIN_PLAIN:
+      hipLaunchKernelGGL((k_verify_main<3, false>), main_grid, dim3(main_b), 0, s, rec, flags, n, verdicts, scratch,
+                         ebp, comb, wcomb);
+      break;
+  }
   return hipGetLastError();
 }
 
