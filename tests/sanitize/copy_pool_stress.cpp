@@ -1,23 +1,17 @@
-// Stress of coa_runtime.cpp's CopyPool (the host copy threads that pack the
+// Stress of csrc/coa_hostpool.h's CopyPool (the host copy threads that pack the
 // aggregation queue's windows): 4 caller threads, each issuing 200 copies of
 // 1-5 MB at once, so several jobs are in progress on the pool together; every
-// copy is compared with its source.  tests/test_sanitizers.py extracts the
-// class text from coa_runtime.cpp into copy_pool_class.inc (the runtime
-// itself needs HIP) and builds this under TSan and under ASan + UBSan.
-#include <algorithm>
+// copy is compared with its source.  The header is host-only (no HIP);
+// tests/test_sanitizers.py builds this under TSan and under ASan + UBSan.
 #include <atomic>
-#include <condition_variable>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <mutex>
 #include <thread>
 #include <vector>
 
-#include "coa_stage.h"  // Seg
-#include "copy_pool_class.inc"
+#include "coa_hostpool.h"
+
+using namespace coa_rt;
 
 int main() {
   std::vector<std::thread> th;

@@ -279,7 +279,7 @@ def _align(x, a=256):
 
 def _workspace_offsets(n):
     """Byte offsets of (flags, slabs) in a caller's workspace of n items
-    (csrc/coa_runtime.cpp ws_carve: k [n][32] | rec [n][128] | flags [2n] |
+    (csrc/coa_sig.cpp ws_carve: k [n][32] | rec [n][128] | flags [2n] |
     [e]B [n][128] | slabs [n][2048], the first three rounded up to 256)."""
     flags = _align(n * 32) + _align(n * 128)
     return flags, flags + _align(2 * n) + n * 128

@@ -75,7 +75,7 @@ def test_ragged_sizes_vs_oracle(engine, sums, n):
     assert (got[cls == -1] == 0).all()
     if n == 769:
         # the records k_pre_halve wrote (workspace: k [n][32] | rec [n][128] | ...,
-        # csrc/coa_runtime.cpp ws_carve): word 24 = H | (d < 0) << 31, words 0..7 /
+        # csrc/coa_sig.cpp ws_carve): word 24 = H | (d < 0) << 31, words 0..7 /
         # 8..15 the digits of c / |d| as nibbles + 8; accepted items only
         rec = ws[_align(n * 32):_align(n * 32) + n * 128].view(np.uint32).reshape(n, 32)[got == 0]
         assert len(rec) > 400

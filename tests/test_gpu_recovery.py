@@ -1,7 +1,7 @@
 """GPU: engine-failure recovery, concurrency of the latency route and
 registration under load.
 
-* Host-pointer calls (coa_runtime.cpp for_shards): with COA_FAULT_SHARD a
+* Host-pointer calls (coa_engine.cpp for_shards): with COA_FAULT_SHARD a
   shard's work is declared failed after it ran; its context is rebuilt (new
   stream, per-call buffers released) and the shard re-run on the next
   context -- verdicts stay bit-exact against the C oracle and

@@ -1,5 +1,5 @@
 """GPU: the exact decision of certificates the fused kernel leaves open
-(coa_runtime.cpp resolve_raw / cert_resolve; the aggregation queue's resolver
+(coa_dag.cpp resolve_raw / cert_resolve; the aggregation queue's resolver
 reaches it through coa_certificate_resolve_raw).
 
 A small round (committee 10, registered) with certificates whose author or

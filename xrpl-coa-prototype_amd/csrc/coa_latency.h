@@ -40,7 +40,7 @@ struct LatArgs {
 hipError_t coa_launch_verify_lat(const LatArgs& a, hipStream_t s);
 
 // The latency kernel over device-resident inputs, enqueued on `stream`
-// (coa_runtime.cpp; the aggregation queue's small signature windows):
+// (coa_sig.cpp; the aggregation queue's small signature windows):
 // d_in [n][128 B] = msg | pk | R | s, d_res [n] words (1 << 8) | verdict.
 // Reads device `device`'s committee key cache: the generation the calling
 // thread pinned (coa_keycache_use, held until the kernel has run), else the

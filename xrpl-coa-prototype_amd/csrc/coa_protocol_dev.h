@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// The protocol table of one key-cache generation (KeySet, coa_runtime.cpp),
+// The protocol table of one key-cache generation (KeySet, coa_engine.h),
 // in the engine's sorted key order.
 struct ProtTab {
   const uint32_t* keys;   // [nk][8]

@@ -68,7 +68,10 @@
 #include <thread>
 #include <vector>
 
+#include "coa_env.h"
 #include "coa_queue.h"
+
+using namespace coa_rt;  // the switch readers of coa_env.h
 
 namespace {
 
@@ -360,8 +363,7 @@ struct Lane {
   }
 
   void start() {
-    int n = 2;
-    if (const char* e = getenv("COA_QUEUE_COLLECTORS")) n = std::max(1, std::min(4, atoi(e)));
+    const int n = (int)env_int("COA_QUEUE_COLLECTORS", 2, 1, 4);
     collectors_live = n;
     for (int i = 0; i < n; i++) collectors.emplace_back([this] { collect(); });
     completer = std::thread([this] { answer(); });
@@ -893,8 +895,7 @@ coa_queue* coa_queue_create(size_t max_batch, uint32_t max_delay_us) {
       // (2 x 32 MB per slot) is never regrown on the launch path.  Unbounded,
       // a backlog at 4,000 batches/s became windows of up to 920 batches
       // (467 MB) whose page-locked regrowth held a window 218-234 ms.
-      const char* e = getenv("COA_QUEUE_DIGEST_MAX");
-      const size_t cap = e ? (size_t)std::max(1, atoi(e)) : 96;
+      const size_t cap = (size_t)env_int("COA_QUEUE_DIGEST_MAX", 96, 1, 0x7fffffff);
       L.max_batch = std::min(L.max_batch, cap);
     }
     L.max_delay = std::chrono::microseconds(max_delay_us);
@@ -905,15 +906,14 @@ coa_queue* coa_queue_create(size_t max_batch, uint32_t max_delay_us) {
     L.reserve_items = 2 * std::min<size_t>(L.max_batch, 65536);
     L.backlog_batch = k == coa_q::LANE_DIGEST ? L.max_batch
                                               : std::max<size_t>(L.max_batch, std::min<size_t>(2 * L.max_batch, 65536));
-    if (const char* e = getenv("COA_QUEUE_BACKLOG_BATCH")) {
-      const long long v = atoll(e);
-      L.backlog_batch = v <= 0 ? L.max_batch : std::max<size_t>(L.max_batch, (size_t)v);
-    }
-    if (const char* e = getenv("COA_QUEUE_BACKLOG_MIN")) L.backlog_min = std::max(0.0, atof(e));
-    if (const char* e = getenv("COA_QUEUE_HELPERS")) L.n_helpers = std::max(0, std::min(15, atoi(e)));
-    if (const char* e = getenv("COA_QUEUE_IDLE_LAUNCH")) L.idle_launch = (size_t)std::max(0, std::min(64, atoi(e)));
-    if (const char* e = getenv("COA_QUEUE_DIRECT")) L.direct_ok = e[0] != '0';
-    if (const char* e = getenv("COA_QUEUE_TRACE_SLOW_US")) L.trace_slow_us = atof(e);
+    // each switch, where set, replaces the default above
+    const long bb = env_int("COA_QUEUE_BACKLOG_BATCH", (long)L.backlog_batch);
+    L.backlog_batch = bb <= 0 ? L.max_batch : std::max<size_t>(L.max_batch, (size_t)bb);
+    L.backlog_min = std::max(0.0, env_double("COA_QUEUE_BACKLOG_MIN", L.backlog_min));
+    L.n_helpers = (int)env_int("COA_QUEUE_HELPERS", L.n_helpers, 0, 15);
+    L.idle_launch = (size_t)env_int("COA_QUEUE_IDLE_LAUNCH", (long)L.idle_launch, 0, 64);
+    L.direct_ok = env_on("COA_QUEUE_DIRECT", L.direct_ok);
+    L.trace_slow_us = env_double("COA_QUEUE_TRACE_SLOW_US", L.trace_slow_us);
     L.be.reset(coa_q::make_backend(k));
     // COA_QUEUE_LANES=verify|digest|verify,digest (read at creation; default
     // both): the lanes set up now -- streams, their first dispatch, staging
@@ -921,7 +921,7 @@ coa_queue* coa_queue_create(size_t max_batch, uint32_t max_delay_us) {
     // a digest slot 64 + 64 MB; four verify and eight digest slots per GPU).  A primary that never
     // hashes worker batches, or a worker that never verifies, names its lane;
     // the other is set up by its first window (which then waits ~25-75 ms).
-    const char* lanes = getenv("COA_QUEUE_LANES");
+    const char* lanes = env_str("COA_QUEUE_LANES");
     const bool warm = !lanes || std::strstr(lanes, k == coa_q::LANE_DIGEST ? "digest" : "verify") != nullptr;
     if (warm) {
       L.be->prepare(L.backlog_batch);

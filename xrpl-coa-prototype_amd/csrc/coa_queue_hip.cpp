@@ -81,6 +81,7 @@
 #include <vector>
 
 #include "coa_committee.h"
+#include "coa_env.h"
 #include "coa_latency.h"
 #include "coa_qstage.h"
 #include "coa_queue.h"
@@ -97,6 +98,8 @@
 // not slower than k_msg_verify, for headers and for votes
 // (profiles/queue_message_ab.json)
 #define COA_QUEUE_MSG_LAT_MAX_DEFAULT 512
+
+using namespace coa_rt;  // the switch readers of coa_env.h
 
 namespace {
 
@@ -268,14 +271,12 @@ int make_stream(Slot& sl) {
 // streams: CU-masked stream creation under its tracer is what faulted in
 // round 5 (see stream_pool), and the kernels -- what a profile measures --
 // are the same on either kind.
-bool under_rocprofiler() { return getenv("ROCP_TOOL_LIBRARIES") || getenv("ROCPROFILER_LIBRARY_CTOR"); }
+bool under_rocprofiler() { return env_str("ROCP_TOOL_LIBRARIES") || env_str("ROCPROFILER_LIBRARY_CTOR"); }
 
 int stream_kind_env() {
-  const char* e = getenv("COA_QUEUE_STREAMS");
-  if (!e) return under_rocprofiler() ? COA_QUEUE_STREAM_PLAIN : COA_QUEUE_STREAM_CUMASK;
-  const std::string v(e);
-  if (v == "plain") return COA_QUEUE_STREAM_PLAIN;
-  if (v == "priority") return COA_QUEUE_STREAM_PRIORITY;
+  if (!env_str("COA_QUEUE_STREAMS")) return under_rocprofiler() ? COA_QUEUE_STREAM_PLAIN : COA_QUEUE_STREAM_CUMASK;
+  if (env_is("COA_QUEUE_STREAMS", "plain")) return COA_QUEUE_STREAM_PLAIN;
+  if (env_is("COA_QUEUE_STREAMS", "priority")) return COA_QUEUE_STREAM_PRIORITY;
   return COA_QUEUE_STREAM_CUMASK;
 }
 
@@ -298,7 +299,7 @@ void free_slot(Slot& sl) {
 class HipBackend : public coa_q::Backend {
  public:
   explicit HipBackend(int lane) : lane_(lane) {
-    if (const char* e = getenv("COA_QUEUE_MSG_LAT_MAX")) msg_lat_max_ = (size_t)strtoull(e, nullptr, 10);
+    msg_lat_max_ = (size_t)env_u64("COA_QUEUE_MSG_LAT_MAX", msg_lat_max_);
   }
   ~HipBackend() override {
     for (Slot& sl : slots_) free_slot(sl);
@@ -483,13 +484,11 @@ class HipBackend : public coa_q::Backend {
     // the verify lane, COA_QUEUE_DIGEST_SLOTS for the digest lane;
     // tools/queue_probe.c measures the choice)
     size_t per = lane_ == coa_q::LANE_DIGEST ? COA_QUEUE_DIGEST_SLOTS_DEFAULT : COA_QUEUE_SLOTS_DEFAULT;
-    if (const char* e = getenv(lane_ == coa_q::LANE_DIGEST ? "COA_QUEUE_DIGEST_SLOTS" : "COA_QUEUE_SLOTS")) {
-      const int v = atoi(e);
-      if (v >= 1 && v <= 8) per = (size_t)v;
-    }
-    if (const char* e = getenv("COA_QUEUE_FAULT")) fault_every_ = strtoull(e, nullptr, 10);
+    const long v = env_int(lane_ == coa_q::LANE_DIGEST ? "COA_QUEUE_DIGEST_SLOTS" : "COA_QUEUE_SLOTS", 0);
+    if (v >= 1 && v <= 8) per = (size_t)v;  // anything else: the default
+    fault_every_ = env_u64("COA_QUEUE_FAULT", fault_every_);
     // COA_QUEUE_INLINE=0: small signature windows take the staged path too (A/B)
-    if (const char* e = getenv("COA_QUEUE_INLINE")) inline_ok_ = e[0] != '0';
+    inline_ok_ = env_on("COA_QUEUE_INLINE", inline_ok_);
     // COA_QUEUE_KEYSORT=0|1: certificate windows of >= 16,384 jobs take their
     // jobs in committee-key order (coa_certificate_verify_many_device_order).
     // Default on: round 6's same-box A/B of the streamed C3 lines was within
@@ -497,7 +496,7 @@ class HipBackend : public coa_q::Backend {
     // translation misses fall from ~50 % to ~1.5 % of requests in key order
     // (round 5); coa_committee.hip's note that queue windows do not sort
     // predates this switch
-    if (const char* e = getenv("COA_QUEUE_KEYSORT")) keysort_ = e[0] != '0';
+    keysort_ = env_on("COA_QUEUE_KEYSORT", keysort_);
     kind_ = stream_kind_env();
     slots_.resize(per * devs_.size());
     // (page-locked staging is sized by prepare(): a reallocation on the

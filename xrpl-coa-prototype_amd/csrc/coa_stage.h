@@ -1,4 +1,4 @@
-// What a shard's staging block holds and how it is packed (coa_runtime.cpp):
+// What a shard's staging block holds and how it is packed (coa_dag.cpp):
 // the arrays of certificates or messages [lo, hi) of a host-pointer call,
 // carved into one block that crosses to the device with ONE copy.  Host code
 // only (no HIP), so tests/sanitize/stage_driver.cpp builds it with plain g++.
@@ -34,7 +34,7 @@ struct Carve {
   }
 };
 
-// One host copy (CopyPool, coa_runtime.cpp).
+// One host copy (CopyPool, coa_hostpool.h).
 struct Seg {
   void* dst;
   const void* src;

@@ -2,7 +2,7 @@
 
 No data-path collective: every shard is verified independently and verdicts
 are written in place.  The same split is implemented natively for in-process
-multi-GPU calls in csrc/coa_runtime.cpp (`shard`)."""
+multi-GPU calls in csrc/coa_engine.cpp (`shard`)."""
 
 
 def shard_ranges(n, parts):
