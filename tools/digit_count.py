@@ -5,8 +5,9 @@ blocks assembled into `.subsection 1` are left out): the outermost loop of the
 kernel is the digit loop, the loop nested in it the three-pass doubling loop,
 so one digit issues  body(outer) - body(inner) + 3 * body(inner)  instructions
 (the body includes the conversion that every digit but the last ends with).
-k_verify_main_sums has one digit loop per role: the consumer's is the one with
-the doubling loop nested in it, the producer's the one without.
+k_verify_main_sums has one digit loop per role (the outermost loops with a
+barrier in them): the consumer's is the one with the doubling loop nested in
+it, the producer's the one without.
 Also prints the straight-line hot-path count of both k_pre_halve<3, *>
 instances and the register, spill, scratch and LDS figures of every kernel in
 the file's metadata.
@@ -122,6 +123,9 @@ def sums_digit(text):
     lines = function_lines(text, SUMS)
     ls = loops(lines)
     top = [r for r in ls if not any(o != r and o[0] <= r[0] and r[1] <= o[1] for o in ls)]
+    # a role's digit loop ends each iteration with the barrier; the consumer's
+    # row prologue (coa_sums_tail.h) has loops too, and no barrier
+    top = [r for r in top if any(op == "s_barrier" for _, op, _ in lines[r[0]:r[1] + 1])]
     cons = [r for r in top if inner_of(ls, r)]
     prod = [r for r in top if not inner_of(ls, r)]
     if len(cons) != 1 or len(prod) != 1:

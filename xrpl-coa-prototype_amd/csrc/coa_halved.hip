@@ -47,6 +47,7 @@
 #include "coa_sc.h"
 #include "coa_sha512.h"
 #include "coa_smul.h"
+#include "coa_sums_tail.h"
 
 using namespace coa_halve;
 
@@ -548,7 +549,8 @@ __global__ void __launch_bounds__(128, 2) k_verify_main2(const uint32_t* __restr
 // pos & 1 while the producer writes digit pos - 1 into the other, then one
 // barrier.
 // Every wave of the workgroup executes the same barriers: H is the maximum
-// over all eight waves (through LDS), dead lanes and rejected items run the
+// over all eight waves (through LDS), capped at COA_SUMS_CAP with the digits
+// above it in the consumers' row prologue; dead lanes and rejected items run the
 // loop with zero digits (their loads then read tab2_identity only), and no
 // wave returns before the loop ends.
 // PRIO: 0 none; 1 / 2 raise the consumers' / the producers' wave priority.
@@ -566,7 +568,7 @@ __global__ void __launch_bounds__(512) k_verify_main_sums(const uint32_t* __rest
                                                           const uint8_t* __restrict__ flags, uint32_t n,
                                                           uint8_t* __restrict__ verdicts,
                                                           const uint32_t* __restrict__ scr,
-                                                          const uint32_t* __restrict__ ebp) {
+                                                          const uint32_t* __restrict__ ebp, int tail_max) {
   __shared__ uint32_t s_lds[2][32][256];  // 64 KiB; the H exchange borrows s_lds[0][0][0..7] first
   const uint32_t slot_item = threadIdx.x & 255u;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
@@ -579,15 +581,28 @@ __global__ void __launch_bounds__(512) k_verify_main_sums(const uint32_t* __rest
   const uint32_t meta0 = myrec[24];
   const bool ok = live && fl == 0x0101u;
   const uint32_t meta = ok ? meta0 : 0u;
-  // H over the whole workgroup, so that all eight waves loop equally often
-  const int hw = wave_max((int)(meta & 0xffu));
-  if ((threadIdx.x & 63u) == 0) s_lds[0][0][wave] = (uint32_t)hw;
+  // H over the whole workgroup, so that all eight waves loop equally often,
+  // and with it (bits 8 and up) the most lanes above COA_SUMS_CAP digits of
+  // any wave
+  const int hi = (int)(meta & 0xffu);
+  const int hw = wave_max(hi);
+  const int tw = __popcll(__builtin_amdgcn_ballot_w64(hi > COA_SUMS_CAP));
+  if ((threadIdx.x & 63u) == 0) s_lds[0][0][wave] = (uint32_t)(hw | tw << 8);
   __syncthreads();
-  int H = 0;
+  int Hwg = 0, tails = 0;
 #pragma unroll
-  for (int w = 0; w < 8; w++) H = max(H, (int)s_lds[0][0][w]);
-  H = __builtin_amdgcn_readfirstlane(H);
+  for (int w = 0; w < 8; w++) {
+    const uint32_t v = s_lds[0][0][w];
+    Hwg = max(Hwg, (int)(v & 0xffu));
+    tails = max(tails, (int)(v >> 8));
+  }
+  Hwg = __builtin_amdgcn_readfirstlane(Hwg);
+  tails = __builtin_amdgcn_readfirstlane(tails);
   __syncthreads();  // the exchange words are read before the first sum overwrites them
+  // The loop runs at most COA_SUMS_CAP digits: a lane with more (a tail lane)
+  // gets its top digits from the row prologue below (coa_sums_tail.h), unless
+  // a wave has more than tail_max of them -- then the loop runs Hwg digits.
+  const int H = tails <= tail_max ? min(Hwg, COA_SUMS_CAP) : Hwg;
   if constexpr (PRIO != 0) {
     if (producer == (PRIO == 2)) __builtin_amdgcn_s_setprio(2);
   }
@@ -642,6 +657,10 @@ __global__ void __launch_bounds__(512) k_verify_main_sums(const uint32_t* __rest
   fe_set(t.Y, 1);
   fe_set(t.Z, 1);
   fe_set(t.T, 1);
+  // tail lanes start from 16 * (their digits at positions >= H): the first
+  // iteration below does not double.  H < Hwg is uniform over the workgroup;
+  // no barrier inside.
+  if (H < Hwg) sums_tail::prologue(acc3, hi > H, i, meta, rec, scr, H);
   __syncthreads();
 #pragma unroll 1
   for (int pos = H - 1; pos >= 0; pos--) {
@@ -828,6 +847,9 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   const CoaMainKernel kernel =
       coa_pick_main(n, one_wave_per_simd_items(), ebp != nullptr, coa_env_switch(getenv("COA_MAIN_IL")),
                     coa_env_switch(getenv("COA_MAIN_TWO")), coa_env_switch(getenv("COA_MAIN_SUMS")));
+  // COA_SUMS_TAIL_MAX, read per call (A/B and tests): coa_sums_tail.h
+  const char* tm = getenv("COA_SUMS_TAIL_MAX");
+  const int tail_max = tm ? atoi(tm) : COA_SUMS_TAIL_MAX;
   // phase 1 stores table 1 in the form the main kernel launched below reads
   if (kernel == COA_MAIN_SUMS)
     hipLaunchKernelGGL((k_pre_halve<3, true>), dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned,
@@ -841,7 +863,7 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   switch (kernel) {
     case COA_MAIN_SUMS:
       hipLaunchKernelGGL((k_verify_main_sums<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512), 0,
-                         s, rec, flags, n, verdicts, scratch, ebp);
+                         s, rec, flags, n, verdicts, scratch, ebp, tail_max);
       break;
     case COA_MAIN_TWO:
       hipLaunchKernelGGL(k_verify_main2, dim3((n + 63) / 64), dim3(128), 0, s, rec, flags, n, verdicts, scratch, ebp);
