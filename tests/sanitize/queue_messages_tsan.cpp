@@ -13,7 +13,7 @@
 // Build (tests/test_queue_messages.py): clang++ -fsanitize=thread, and g++
 // -fsanitize=address,undefined, coa_queue.cpp queue_messages_tsan.cpp.
 // usage: queue_messages_tsan <producers> <requests per producer>
-//        [fail every k-th launch] [1: every retry fails too]
+//        [fail every k-th launch] [1: every retry fails too] [1: every resolver pass fails]
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -33,6 +33,11 @@ static std::atomic<long> g_engine_calls{0}, g_injected{0}, g_resolver_passes{0},
 static std::atomic<long> g_lat_windows{0}, g_tp_windows{0};
 static unsigned long g_fault_every = 0;
 static bool g_fault_all = false;
+// argv[5] = 1: resolve() writes its outputs and then returns COA_EHIP, as a
+// HIP error in the resolver's engine call would; every request it was given
+// must then be answered with that status and its kind's "failed" value
+static bool g_resolve_fails = false;
+static std::atomic<long> g_open_errors{0};
 static uint8_t v_single(const uint8_t* msg, const uint8_t* sig) { return (uint8_t)((msg[0] ^ sig[0]) & 1u); }
 static uint8_t v_group(const uint8_t* msg, size_t nvotes) { return (uint8_t)((msg[1] + nvotes) & 1u); }
 static uint8_t v_cert(const uint8_t* id, size_t nvotes) { return (uint8_t)((id[2] + nvotes) & 7u); }
@@ -161,7 +166,7 @@ class StubBackend : public coa_q::Backend {
           g_resolved++;
         }
     }
-    return COA_OK;
+    return g_resolve_fails ? COA_EHIP : COA_OK;
   }
 
  private:
@@ -179,6 +184,8 @@ coa_q::Backend* coa_q::make_backend(int) { return new StubBackend(); }
 struct Req {
   uint8_t expect[32];
   size_t n_expect;
+  bool open = false;   // the stub leaves it to resolve()
+  uint8_t failed = 0;  // the kind's "failed" value
   std::atomic<int> done{0};
   std::atomic<int> bad{0};
 };
@@ -186,7 +193,11 @@ struct Req {
 static std::atomic<long> g_engine_errors{0};
 static void check_cb(void* user, int status, const uint8_t* verdicts, size_t n) {
   Req* r = static_cast<Req*>(user);
-  if (status == COA_EHIP) {
+  if (g_resolve_fails && r->open) {
+    // from the failed resolver pass, or from a window whose every attempt failed
+    if (status != COA_EHIP || n != 1 || verdicts[0] != r->failed) r->bad++;
+    g_open_errors++;
+  } else if (status == COA_EHIP) {
     g_engine_errors++;
     if (!g_fault_all) r->bad++;
   } else if (status != COA_OK || n != r->n_expect || std::memcmp(verdicts, r->expect, n) != 0) {
@@ -200,6 +211,7 @@ int main(int argc, char** argv) {
   const int per = argc > 2 ? std::atoi(argv[2]) : 400;
   g_fault_every = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 0;
   g_fault_all = argc > 4 && std::atoi(argv[4]) == 1;
+  g_resolve_fails = argc > 5 && std::atoi(argv[5]) == 1;
   coa_queue* q = coa_queue_create(64, 200);
   std::vector<std::vector<Req>> reqs(producers);
   for (auto& v : reqs) v = std::vector<Req>(per);
@@ -226,6 +238,7 @@ int main(int argc, char** argv) {
             const size_t nv = rng() % 5;
             std::vector<uint8_t> pks(nv * 32 + 1, 1), sigs(nv * 64 + 1, 2);
             r.expect[0] = v_group(a, nv);
+            r.open = true, r.failed = 1;
             rc = coa_queue_submit_batch(q, a, pks.data(), sigs.data(), nv, check_cb, &r);
             break;
           }
@@ -233,6 +246,7 @@ int main(int argc, char** argv) {
             const size_t nv = rng() % 4;
             std::vector<uint8_t> hdr(rng() % 100), pks(nv * 32 + 1, 3), sigs(nv * 64 + 1, 4);
             r.expect[0] = v_cert(a, nv);
+            r.open = (a[3] & 1u) != 0, r.failed = 7;
             rc = coa_queue_submit_certificate(q, hdr.data(), hdr.size(), a, c, b, 9, pks.data(), sigs.data(), nv,
                                               check_cb, &r);
             break;
@@ -251,6 +265,7 @@ int main(int argc, char** argv) {
             for (auto& x : hdr) x = (uint8_t)rng();
             r.expect[0] = (uint8_t)(v_header_id(hdr.data(), hdr.size(), a) | v_header_sig(a, c, b));
             n_headers++;
+            r.open = defers(c), r.failed = 3;
             if (defers(c)) n_deferred_msgs++;
             rc = coa_queue_submit_header(q, hdr.data(), hdr.size(), a, c, b, check_cb, &r);
             break;
@@ -259,6 +274,7 @@ int main(int argc, char** argv) {
             const uint64_t round = ((uint64_t)rng() << 32) | rng();
             r.expect[0] = v_vote(a, round, d, c, b);
             n_votes++;
+            r.open = defers(c), r.failed = 1;
             if (defers(c)) n_deferred_msgs++;
             rc = coa_queue_submit_vote(q, a, round, d, c, b, check_cb, &r);
             break;
@@ -294,11 +310,12 @@ int main(int argc, char** argv) {
   const long total = (long)producers * per;
   std::printf("queue messages: %ld/%ld answered, %ld wrong, %llu headers, %llu votes, %llu launches, injected %ld, "
               "retried %llu, recovered %llu, failed %llu, engine errors %ld, deferred %llu in %llu passes, message "
-              "windows %llu latency %llu throughput\n",
+              "windows %llu latency %llu throughput, resolver errors %ld\n",
               done, total, bad, (unsigned long long)headers, (unsigned long long)votes, (unsigned long long)launches,
               g_injected.load(), (unsigned long long)m.retried_windows, (unsigned long long)m.recovered_windows,
               (unsigned long long)m.failed_windows, g_engine_errors.load(), (unsigned long long)m.deferred_requests,
-              (unsigned long long)m.resolver_passes, (unsigned long long)lat_w, (unsigned long long)tp_w);
+              (unsigned long long)m.resolver_passes, (unsigned long long)lat_w, (unsigned long long)tp_w,
+              g_open_errors.load());
   const bool recovery_ok =
       m.retried_windows == (uint64_t)g_injected.load() &&
       (g_fault_all ? (m.recovered_windows == 0 && m.failed_windows == m.retried_windows &&
@@ -316,7 +333,14 @@ int main(int argc, char** argv) {
                           headers > 0 && votes > 0 && n_deferred_msgs.load() > 0 && lat_w + tp_w > 0 &&
                           lat_w + tp_w <= m.windows && lat_w == (uint64_t)g_lat_windows.load() &&
                           tp_w == (uint64_t)g_tp_windows.load();
-  const bool metrics_ok = m.requests == (uint64_t)total && m.signatures == items && items >= headers + votes &&
+  // a failed resolver pass answered exactly the requests it was given (with
+  // failed windows, their open requests got the same answer from the window)
+  const long open_errors = g_open_errors.load(), resolved = g_resolved.load();
+  const bool open_ok = !g_resolve_fails ? open_errors == 0
+                       : g_fault_all    ? open_errors > 0 && open_errors >= resolved
+                                        : open_errors > 0 && open_errors == resolved;
+  const bool metrics_ok = open_ok && m.requests == (uint64_t)total &&
+                          m.signatures == items && items >= headers + votes &&
                           m.windows == launches && recovery_ok && defer_ok && message_ok;
   return (done == total && bad == 0 && items + groups + digests == (uint64_t)total && metrics_ok) ? 0 : 1;
 }

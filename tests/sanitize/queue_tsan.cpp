@@ -7,6 +7,7 @@
 //
 // Build (tests/test_sanitizers.py): g++ -fsanitize=thread coa_queue.cpp
 // queue_tsan.cpp.  usage: queue_tsan <producers> <requests per producer>
+//        [fail every k-th launch] [1: every retry fails too] [1: every resolver pass fails]
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -33,6 +34,11 @@
 static std::atomic<long> g_engine_calls{0}, g_injected{0}, g_resolver_passes{0}, g_resolved{0};
 static unsigned long g_fault_every = 0;
 static bool g_fault_all = false;
+// argv[5] = 1: resolve() writes its outputs and then returns COA_EHIP, as a
+// HIP error in the resolver's engine call would; every request it was given
+// must then be answered with that status and its kind's "failed" value
+static bool g_resolve_fails = false;
+static std::atomic<long> g_open_errors{0};
 static uint8_t v_single(const uint8_t* msg, const uint8_t* sig) { return (uint8_t)((msg[0] ^ sig[0]) & 1u); }
 static uint8_t v_group(const uint8_t* msg, size_t nvotes) { return (uint8_t)((msg[1] + nvotes) & 1u); }
 static uint8_t v_cert(const uint8_t* id, size_t nvotes) { return (uint8_t)((id[2] + nvotes) & 7u); }
@@ -121,7 +127,7 @@ class StubBackend : public coa_q::Backend {
           g_resolved++;
         }
     }
-    return COA_OK;
+    return g_resolve_fails ? COA_EHIP : COA_OK;
   }
 
  private:
@@ -139,6 +145,8 @@ coa_q::Backend* coa_q::make_backend(int) { return new StubBackend(); }
 struct Req {
   uint8_t expect[32];
   size_t n_expect;
+  bool open = false;   // the stub leaves it to resolve()
+  uint8_t failed = 0;  // the kind's "failed" value
   std::vector<uint8_t> hold;  // a borrowed certificate's bytes, valid until the end of the run
   std::atomic<int> done{0};
   std::atomic<int> bad{0};
@@ -147,7 +155,11 @@ struct Req {
 static std::atomic<long> g_engine_errors{0};
 static void check_cb(void* user, int status, const uint8_t* verdicts, size_t n) {
   Req* r = static_cast<Req*>(user);
-  if (status == COA_EHIP) {
+  if (g_resolve_fails && r->open) {
+    // from the failed resolver pass, or from a window whose every attempt failed
+    if (status != COA_EHIP || n != 1 || verdicts[0] != r->failed) r->bad++;
+    g_open_errors++;
+  } else if (status == COA_EHIP) {
     g_engine_errors++;
     if (!g_fault_all) r->bad++;
   } else if (status != COA_OK || n != r->n_expect || std::memcmp(verdicts, r->expect, n) != 0) {
@@ -161,6 +173,7 @@ int main(int argc, char** argv) {
   const int per = argc > 2 ? std::atoi(argv[2]) : 400;
   g_fault_every = argc > 3 ? std::strtoul(argv[3], nullptr, 10) : 0;
   g_fault_all = argc > 4 && std::atoi(argv[4]) == 1;
+  g_resolve_fails = argc > 5 && std::atoi(argv[5]) == 1;
   coa_queue* q = coa_queue_create(64, 200);
   std::vector<std::vector<Req>> reqs(producers);
   for (auto& v : reqs) v = std::vector<Req>(per);
@@ -186,6 +199,7 @@ int main(int argc, char** argv) {
             std::vector<uint8_t> pks(nv * 32 + 1, 1), sigs(nv * 64 + 1, 2);
             r.n_expect = 1;
             r.expect[0] = v_group(a, nv);
+            r.open = true, r.failed = 1;
             rc = coa_queue_submit_batch(q, a, pks.data(), sigs.data(), nv, check_cb, &r);
             break;
           }
@@ -194,6 +208,7 @@ int main(int argc, char** argv) {
             std::vector<uint8_t> hdr(rng() % 100), pks(nv * 32 + 1, 3), sigs(nv * 64 + 1, 4);
             r.n_expect = 1;
             r.expect[0] = v_cert(a, nv);
+            r.open = (a[3] & 1u) != 0, r.failed = 7;
             if (rng() % 2) {
               rc = coa_queue_submit_certificate(q, hdr.data(), hdr.size(), a, c, b, 9, pks.data(), sigs.data(), nv,
                                                 check_cb, &r);
@@ -252,12 +267,12 @@ int main(int argc, char** argv) {
   const long total = (long)producers * per;
   std::printf("queue tsan: %ld/%ld answered, %ld wrong, %llu launches, %ld windows completed, max in flight %llu, "
               "wait p50 %.0f us p99 %.0f us, injected %ld, retried %llu, recovered %llu, failed %llu, engine errors %ld, "
-              "deferred %llu in %llu passes\n",
+              "deferred %llu in %llu passes, resolver errors %ld\n",
               done, total, bad, (unsigned long long)launches, g_engine_calls.load(),
               (unsigned long long)m.max_in_flight, m.wait_us_p50, m.wait_us_p99, g_injected.load(),
               (unsigned long long)m.retried_windows, (unsigned long long)m.recovered_windows,
               (unsigned long long)m.failed_windows, g_engine_errors.load(), (unsigned long long)m.deferred_requests,
-              (unsigned long long)m.resolver_passes);
+              (unsigned long long)m.resolver_passes, g_open_errors.load());
   // every injected failure was retried; retries succeed unless told not to
   const bool recovery_ok =
       m.retried_windows == (uint64_t)g_injected.load() &&
@@ -269,7 +284,14 @@ int main(int argc, char** argv) {
   const bool defer_ok = m.deferred_requests == (uint64_t)g_resolved.load() &&
                         m.resolver_passes == (uint64_t)g_resolver_passes.load() &&
                         m.deferred_requests > 0;
-  const bool metrics_ok = m.requests == (uint64_t)total && m.batches + m.certificates + m.digests <= (uint64_t)total &&
+  // a failed resolver pass answered exactly the requests it was given (with
+  // failed windows, their open requests got the same answer from the window)
+  const long open_errors = g_open_errors.load(), resolved = g_resolved.load();
+  const bool open_ok = !g_resolve_fails ? open_errors == 0
+                       : g_fault_all    ? open_errors > 0 && open_errors >= resolved
+                                        : open_errors > 0 && open_errors == resolved;
+  const bool metrics_ok = open_ok && m.requests == (uint64_t)total &&
+                          m.batches + m.certificates + m.digests <= (uint64_t)total &&
                           m.windows == launches && recovery_ok && defer_ok;
   return (done == total && bad == 0 && items + groups + digests == (uint64_t)total && metrics_ok) ? 0 : 1;
 }

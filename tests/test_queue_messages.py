@@ -6,7 +6,9 @@
   and under ASan + UBSan: 16 producers submit all six request kinds, the stub
   defers messages by a byte of the author so the resolver answers them, and
   launch failures are injected (every 7th launch re-run and exact; every retry
-  failing too: the engine error reaches those callbacks).  Nothing is loaded
+  failing too: the engine error reaches those callbacks; every resolver pass
+  failing: its requests get the error with their kinds' "failed" values).
+  Nothing is loaded
   into Python and nothing is preloaded.
 * With no GPU the futures of submit_header / submit_vote raise EngineError and
   the queue's counters count the requests."""
@@ -52,6 +54,12 @@ def _check_runs(exe, env):
     # ... and with every retry failing too, those callbacks get the engine error
     out = _run([exe, "8", "300", "7", "1"], env)
     assert "2400/2400 answered, 0 wrong" in out and "recovered 0," in out and "engine errors 0," not in out, out
+    # every resolver pass fails: each request left to it gets the engine error
+    # with its kind's "failed" value (7 certificate, 3 header, 1 vote or bare
+    # batch; the binary checks each callback), every other request is exact
+    out = _run([exe, "16", "300", "7", "0", "1"], env)
+    assert "4800/4800 answered, 0 wrong" in out and "resolver errors 0\n" not in out, out
+    assert "engine errors 0," in out and "deferred 0 " not in out, out
     # idle launch: windows also launched by the submitting threads
     out = _run([exe, "16", "300", "7"], dict(env, COA_QUEUE_IDLE_LAUNCH="1"))
     assert "4800/4800 answered, 0 wrong" in out and "injected 0," not in out, out

@@ -13,7 +13,9 @@
   (same two-slot double buffering), with 16 producer threads submitting
   every request kind while they also flush and read the stats and metrics,
   and with injected launch failures (engine-failure recovery: re-run and
-  exact, or reported to every callback when every attempt fails).
+  exact, or reported to every callback when every attempt fails) and with
+  failing resolver passes (the error and the "failed" value of its kind to
+  each request the pass was given).
 No device code is involved (GPU sanitizers are not available on the pool)."""
 import os
 import subprocess
@@ -71,6 +73,10 @@ def test_queue_many_producers_tsan():
     # retried == recovered == injected and no callback saw an engine error)
     out = _run([exe, "16", "500", "7"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"})
     assert "8000/8000 answered, 0 wrong" in out and "injected 0," not in out, out
+    # every resolver pass fails: each request left to it gets the engine error
+    # with its kind's "failed" value (the binary checks both), the rest exact
+    out = _run([exe, "16", "300", "7", "0", "1"], {"TSAN_OPTIONS": "halt_on_error=1:second_deadlock_stack=1"})
+    assert "4800/4800 answered, 0 wrong" in out and "resolver errors 0\n" not in out, out
     # idle launch: windows also launched by submitting threads that find the
     # engine idle (beside the collector), with and without injected failures
     for k in ("1", "2"):
@@ -92,6 +98,10 @@ def test_queue_many_producers_asan_ubsan():
     # get the engine error (counted as failed windows), the rest are exact
     out = _run([exe, "8", "300", "5", "1"], env)
     assert "2400/2400 answered, 0 wrong" in out and "recovered 0" in out and "engine errors 0" not in out, out
+    # every resolver pass fails: its requests get the engine error and their
+    # kinds' "failed" values, every other request its exact verdict
+    out = _run([exe, "16", "300", "0", "0", "1"], env)
+    assert "4800/4800 answered, 0 wrong" in out and "resolver errors 0\n" not in out, out
     out = _run([exe, "16", "500"], dict(env, COA_QUEUE_IDLE_LAUNCH="1"))
     assert "8000/8000 answered, 0 wrong" in out, out
 

@@ -69,13 +69,16 @@
 #include <vector>
 
 #include "coa_env.h"
+#include "coa_qmetrics.h"
 #include "coa_queue.h"
 
 using namespace coa_rt;  // the switch readers of coa_env.h
 
 namespace {
 
+using coa_q::LaneMetrics;
 using coa_q::Launch;
+using coa_q::WaitTally;
 using coa_q::Window;
 
 enum Kind : uint8_t { K_VERIFY, K_BATCH, K_CERT, K_DIGEST, K_HEADER, K_VOTE };
@@ -101,6 +104,33 @@ struct Req {
   uint32_t n;      // K_VERIFY: consecutive signatures of the request
   Kind kind;
 };
+
+// Where each kind's answer is -- the only per-kind tables of the outputs, for
+// the completer and the resolver alike.  True for a request the backend left
+// open in its window (Window::c_defer, m_defer, g_defer): the resolver's.
+inline bool is_deferred(const Req& r, const Window& w) {
+  switch (r.kind) {
+    case K_CERT: return w.is_deferred_cert(r.idx);
+    case K_BATCH: return w.g_defer;
+    case K_HEADER: return w.is_deferred_msg(r.idx);
+    case K_VOTE: return w.is_deferred_msg((uint32_t)w.nhd + r.idx);
+    case K_VERIFY:
+    case K_DIGEST: break;
+  }
+  return false;
+}
+// The request's callback with the launch's (or the resolver pass's) status
+// and its output in the window.
+inline void answer_req(const Req& r, const Window& w, int rc) {
+  switch (r.kind) {
+    case K_VERIFY: r.cb(r.user, rc, w.v_out.data() + r.idx, r.n); break;
+    case K_BATCH: r.cb(r.user, rc, w.g_out.data() + r.idx, 1); break;
+    case K_CERT: r.cb(r.user, rc, w.c_out.data() + r.idx, 1); break;
+    case K_DIGEST: r.cb(r.user, rc, w.d_out.data() + (size_t)r.idx * 32, 32); break;
+    case K_HEADER: r.cb(r.user, rc, w.hd_out.data() + r.idx, 1); break;
+    case K_VOTE: r.cb(r.user, rc, w.vt_out.data() + r.idx, 1); break;
+  }
+}
 
 constexpr size_t kShards = 64;  // intake shards per queue
 // bounded spins around a shard's lock: the collector's pause-spin on try_lock
@@ -130,9 +160,49 @@ struct alignas(64) Shard {
   // producers copied at ~3 GB/s, the collector's take cost 60-190 us)
   std::vector<std::unique_ptr<Window>> spares;
   std::vector<std::vector<Req>> spare_reqs;
+
+  Shard() { w = fresh(); }  // in the body: fresh() reads spares, declared after w
+  // An empty window: a spare, or a new one (mu held, or nobody else yet).
+  std::unique_ptr<Window> fresh() {
+    std::unique_ptr<Window> f;
+    if (!spares.empty()) {
+      f = std::move(spares.back());
+      spares.pop_back();
+    } else {
+      f.reset(new Window());
+      f->reset();
+    }
+    return f;
+  }
+  // The collector's take (mu held): the filled window and its requests out
+  // (`out` comes in empty), a fresh window and a spare request vector in.
+  std::unique_ptr<Window> take(std::vector<Req>& out) {
+    std::unique_ptr<Window> full = std::move(w);
+    out.swap(reqs);
+    w = fresh();
+    if (!spare_reqs.empty()) {
+      reqs.swap(spare_reqs.back());
+      spare_reqs.pop_back();
+    }
+    items = reported = 0;
+    return full;
+  }
+  // An answered window and/or request vector (either may be null) back into
+  // the pool: emptied without the lock, kept under mu while fewer than
+  // kSpares are (otherwise left with the caller).
+  void recycle(std::unique_ptr<Window>& win, std::vector<Req>* rq) {
+    if (win) win->reset();
+    if (rq) rq->clear();
+    std::lock_guard<std::mutex> g(mu);
+    if (win && spares.size() < kSpares) spares.push_back(std::move(win));
+    if (rq && spare_reqs.size() < kSpares) spare_reqs.push_back(std::move(*rq));
+  }
 };
 
-// One shard's requests inside a launch.
+// One shard's requests inside a launch.  Also the requests of a part that
+// the backend left open (Window::c_defer, m_defer, g_defer), with the part's
+// window (moved out of the flight, not recycled): the resolver thread decides
+// them, answers their callbacks and returns the window to the shard's pool.
 struct Part {
   std::unique_ptr<Window> w;
   std::vector<Req> reqs;
@@ -145,44 +215,12 @@ struct Flight {
   int64_t t_launch = 0;  // ns, when the collector handed the window to the backend
 };
 
-// A part's requests the backend left open (Window::c_defer, m_defer, g_defer), with
-// the part's window (moved out of the flight, not recycled): the resolver
-// thread decides them and answers their callbacks.
-struct Deferred {
-  std::unique_ptr<Window> w;
-  std::vector<Req> reqs;
-  uint32_t shard;  // the window goes back to this shard's pool once answered
-};
-
-inline bool is_deferred(const Req& r, const Window& w) {
-  return (r.kind == K_CERT && w.is_deferred_cert(r.idx)) || (r.kind == K_BATCH && w.g_defer) ||
-         (r.kind == K_HEADER && w.is_deferred_msg(r.idx)) ||
-         (r.kind == K_VOTE && w.is_deferred_msg((uint32_t)w.nhd + r.idx));
-}
-
 std::atomic<uint64_t> g_queue_ids{1};
 std::atomic<uint32_t> g_thread_ord{0};
 
 uint32_t thread_ordinal() {
   static thread_local const uint32_t ord = g_thread_ord.fetch_add(1, std::memory_order_relaxed);
   return ord;
-}
-
-// Wait-time histogram: bucket 0 is < 1 us; bucket 8e + m + 1 covers
-// [2^e (1 + m/8), 2^e (1 + (m+1)/8)) microseconds (the exponent and the top
-// three mantissa bits of the double: no log per request).
-constexpr int HB = 8 * 40;
-int wait_bucket(double us) {
-  if (!(us >= 1.0)) return 0;
-  uint64_t bits;
-  std::memcpy(&bits, &us, 8);
-  const int e = (int)((bits >> 52) & 0x7ff) - 1023, m = (int)((bits >> 49) & 7);
-  return std::min(HB - 1, 8 * e + m + 1);
-}
-double bucket_mid(int b) {
-  if (b == 0) return 0.5;
-  const int e = (b - 1) / 8, m = (b - 1) % 8;
-  return std::ldexp(1.0 + (m + 0.5) / 8.0, e);
 }
 
 // Callback helpers: the completion thread answers a large launch together
@@ -308,29 +346,14 @@ struct Lane {
   size_t busy = 0;            // windows taken by the collector and not yet answered
   bool flush = false, collector_done = false;
   int collectors_live = 0;  // collector threads not yet exited
-  std::deque<Deferred> open;  // deferred parts waiting for the resolver
-  size_t resolving = 0;       // deferred parts not yet answered (queued or in a pass)
+  std::deque<Part> open;  // deferred parts waiting for the resolver
+  size_t resolving = 0;   // deferred parts not yet answered (queued or in a pass)
   bool resolver_stop = false;
   bool idle() const { return pend.load() <= 0 && busy == 0 && resolving == 0; }
 
-  // metrics (under mu, except m_max_pending)
-  uint64_t m_requests = 0, m_windows = 0, m_sig = 0, m_batch = 0, m_cert = 0, m_dig = 0;
-  uint64_t m_max_window = 0, m_max_in_flight = 0;
-  uint64_t m_retried = 0, m_recovered = 0, m_failed = 0;
+  // metrics: under mu, except m_max_pending (producers raise it without mu)
+  LaneMetrics m{now_ns()};  // epoch_ns; the rest zero
   std::atomic<int64_t> m_max_pending{0};
-  double m_wait_sum = 0.0, m_wait_max = 0.0;
-  uint64_t m_hist[HB] = {};
-  // the slowest window (launch call -> outputs in host memory) and the
-  // longest wait for a free slot
-  double m_window_us_max = 0.0, m_slot_wait_us_max = 0.0;
-  uint64_t m_window_max_items = 0;
-  int64_t m_epoch_ns = now_ns();  // creation or the last reset_metrics
-  double m_window_max_at_ms = 0.0, m_window_max_dev_us = 0.0;
-  uint32_t m_window_max_kinds = 0;
-  uint64_t m_deferred = 0, m_passes = 0;
-  uint64_t m_hdr = 0, m_vote = 0, m_msg_lat = 0, m_msg_tp = 0;  // coa_queue_message_stats
-  double m_resolve_us_max = 0.0;
-  double m_stage_us[COA_QSTAGES] = {};
 
   // COA_QUEUE_COLLECTORS (1..4, default 2; read at creation): collector
   // threads.  A window's pack (its requests' bytes into the slot's
@@ -354,13 +377,6 @@ struct Lane {
   bool direct_ok = true;
   std::mutex gather_mu;  // one gather at a time (the collector, or a submitter launching directly)
   double trace_slow_us = 0;  // COA_QUEUE_TRACE_SLOW_US (read at creation): report slower windows on stderr
-
-  Lane() {
-    for (size_t i = 0; i < kShards; i++) {
-      shards[i].w.reset(new Window());
-      shards[i].w->reset();
-    }
-  }
 
   void start() {
     const int n = (int)env_int("COA_QUEUE_COLLECTORS", 2, 1, 4);
@@ -448,22 +464,9 @@ struct Lane {
         std::lock_guard<std::mutex> l(sh.mu, std::adopt_lock);
         sh.taking.store(false, std::memory_order_release);
         if (sh.items == 0) continue;
-        p.w = std::move(sh.w);
-        p.reqs.swap(sh.reqs);
-        if (!sh.spares.empty()) {
-          sh.w = std::move(sh.spares.back());
-          sh.spares.pop_back();
-        } else {
-          sh.w.reset(new Window());
-          sh.w->reset();
-        }
-        if (!sh.spare_reqs.empty()) {
-          sh.reqs.swap(sh.spare_reqs.back());
-          sh.spare_reqs.pop_back();
-        }
         items = sh.items;
         rep = sh.reported;
-        sh.items = sh.reported = 0;
+        p.w = sh.take(p.reqs);
       }
       pend.fetch_sub((int64_t)rep);
       taken += items;
@@ -507,8 +510,27 @@ struct Lane {
   void launch_window(std::unique_lock<std::mutex>& l) {
     Flight f;
     l.unlock();
-    // every slot busy: wait for one before taking the window, which grows to
-    // backlog_batch items if a backlog built up meanwhile (see backlog_batch)
+    take_window(f);
+    l.lock();
+    if (f.parts.empty()) {  // every pending item was taken by an earlier window
+      busy--;
+      if (idle()) idle_cv.notify_all();
+      return;
+    }
+    m.max_window = std::max<uint64_t>(m.max_window, f.L.items());
+    l.unlock();
+    launch(f);
+    l.lock();
+    m.windows++;
+    flight.push_back(std::move(f));
+    m.max_in_flight = std::max<uint64_t>(m.max_in_flight, flight.size());
+    flight_cv.notify_one();
+  }
+
+  // The pending requests into f (no queue lock).  Every slot busy: waits for
+  // one before taking the window, which grows to backlog_batch items if a
+  // backlog built up meanwhile (see backlog_batch).
+  void take_window(Flight& f) {
     size_t cap = max_batch;
     const int64_t tw = now_ns();
     if (be->wait_free_slot()) {
@@ -521,14 +543,10 @@ struct Lane {
       gather(f, cap);
     }
     f.L.stage_ns[COA_QSTAGE_GATHER] += now_ns() - tg;
-    l.lock();
-    if (f.parts.empty()) {  // every pending item was taken by an earlier window
-      busy--;
-      if (idle()) idle_cv.notify_all();
-      return;
-    }
-    m_max_window = std::max<uint64_t>(m_max_window, f.L.items());
-    l.unlock();
+  }
+
+  // Hands the taken window to the backend (no queue lock).
+  void launch(Flight& f) {
     f.L.reset_outputs();
     f.L.attempts = 1;
     f.t_launch = now_ns();
@@ -541,27 +559,11 @@ struct Lane {
     }
     be->launch(f.L);  // stages and enqueues; blocks only while every slot is busy
     f.L.stage_ns[COA_QSTAGE_SLOT_WAIT] += f.L.slot_wait_ns;
-    l.lock();
-    m_windows++;
-    flight.push_back(std::move(f));
-    m_max_in_flight = std::max<uint64_t>(m_max_in_flight, flight.size());
-    flight_cv.notify_one();
   }
 
-  // A launch that failed on the device (a HIP error or an allocation
-  // failure; not "no device" or bad arguments): retried on the recovery
-  // context of each device in turn (the first retry on the next device),
-  // until one succeeds.
-  static bool recoverable(int rc) { return rc == COA_EHIP || rc == COA_ENOMEM; }
-  void recover(Launch& L) {
-    const int n = std::max(1, be->devices());
-    for (int a = 1; a <= n && recoverable(L.rc); a++) {
-      L.reset_outputs();
-      L.attempts++;
-      be->retry(L, a);
-    }
-  }
-
+  // The completer: per window, in launch order, the steps below.  Callbacks,
+  // then the windows back to their shards, then busy-- / idle_cv: what
+  // coa_queue_flush relies on.
   void answer() {
     t_queue_thread = true;
     std::unique_lock<std::mutex> l(mu);
@@ -573,145 +575,18 @@ struct Lane {
       l.unlock();
       be->complete(f.L);
       const double window_us = (double)(now_ns() - f.t_launch) * 1e-3;
-      if (trace_slow_us > 0 && window_us > trace_slow_us) {  // COA_QUEUE_TRACE_SLOW_US (diagnostics)
-        fprintf(stderr,
-                "[coa queue] slow window %.0f us at t=%.6f s: %zu items kinds %u slot %d; slot_wait %.0f pack %.0f "
-                "enqueue %.0f (pin %.0f h2d %.0f launch %.0f d2h %.0f event %.0f) device_wait %.0f scatter %.0f us\n",
-                window_us, (double)f.t_launch * 1e-9, f.L.items(), f.L.kinds(), f.L.slot,
-                f.L.stage_ns[COA_QSTAGE_SLOT_WAIT] * 1e-3, f.L.stage_ns[COA_QSTAGE_PACK] * 1e-3,
-                f.L.stage_ns[COA_QSTAGE_ENQUEUE] * 1e-3, f.L.enq_ns[Launch::ENQ_PIN] * 1e-3,
-                f.L.enq_ns[Launch::ENQ_H2D] * 1e-3, f.L.enq_ns[Launch::ENQ_LAUNCH] * 1e-3,
-                f.L.enq_ns[Launch::ENQ_D2H] * 1e-3, f.L.enq_ns[Launch::ENQ_EVENT] * 1e-3,
-                f.L.stage_ns[COA_QSTAGE_DEVICE_WAIT] * 1e-3, f.L.stage_ns[COA_QSTAGE_SCATTER] * 1e-3);
-      }
-      const bool retried = recoverable(f.L.rc);
-      if (retried) recover(f.L);
-      const int rc = f.L.rc;
-      // requests the backend left open go to the resolver, the rest are
-      // answered now (a failed window leaves nothing open: every request
-      // gets the error)
-      bool any_defer = false;
-      for (Part& p : f.parts) {
-        if (rc != COA_OK) {
-          p.w->c_defer.clear();
-          p.w->m_defer.clear();
-          p.w->g_defer = false;
-        }
-        any_defer = any_defer || p.w->deferred();
-      }
-      const int64_t tcb = now_ns();
-      // callbacks, in runs of contiguous requests (helpers join for large
-      // launches); wait times from a clock read every 32 requests
-      struct Seg {
-        const Part* p;
-        size_t lo, hi;
-      };
-      std::vector<Seg> segs;
-      size_t nreq = 0;
-      for (const Part& p : f.parts) {
-        for (size_t lo = 0; lo < p.reqs.size(); lo += kRun) segs.push_back({&p, lo, std::min(p.reqs.size(), lo + kRun)});
-        nreq += p.reqs.size();
-      }
-      struct Tally {
-        uint64_t hist[HB] = {};
-        double wsum = 0.0, wmax = 0.0;
-      };
-      std::vector<Tally> tallies(segs.size());
-      auto answer_seg = [&](size_t si) {
-        const Seg& g = segs[si];
-        const Window& w = *g.p->w;
-        Tally& t = tallies[si];
-        int64_t tnow = now_ns();
-        for (size_t k = g.lo; k < g.hi; k++) {
-          const Req& r = g.p->reqs[k];
-          if (any_defer && is_deferred(r, w)) continue;  // the resolver answers it
-          if (((k - g.lo) & 31) == 31) tnow = now_ns();
-          const double us = (double)(tnow - r.t0) * 1e-3;
-          t.wsum += us;
-          t.wmax = std::max(t.wmax, us);
-          t.hist[wait_bucket(us)]++;
-          switch (r.kind) {
-            case K_VERIFY: r.cb(r.user, rc, w.v_out.data() + r.idx, r.n); break;
-            case K_BATCH: r.cb(r.user, rc, w.g_out.data() + r.idx, 1); break;
-            case K_CERT: r.cb(r.user, rc, w.c_out.data() + r.idx, 1); break;
-            case K_DIGEST: r.cb(r.user, rc, w.d_out.data() + (size_t)r.idx * 32, 32); break;
-            case K_HEADER: r.cb(r.user, rc, w.hd_out.data() + r.idx, 1); break;
-            case K_VOTE: r.cb(r.user, rc, w.vt_out.data() + r.idx, 1); break;
-          }
-        }
-      };
-      if (n_helpers > 0 && nreq >= kParallelAnswer && segs.size() > 1) {
-        if (!helpers_on) {
-          helpers.start(n_helpers);
-          helpers_on = true;
-        }
-        helpers.run(segs.size(), answer_seg);
-      } else {
-        for (size_t si = 0; si < segs.size(); si++) answer_seg(si);
-      }
-      f.L.stage_ns[COA_QSTAGE_CALLBACKS] += now_ns() - tcb;
-      uint64_t hist[HB] = {};
-      double wsum = 0.0, wmax = 0.0;
-      for (const Tally& t : tallies) {
-        for (int b = 0; b < HB; b++) hist[b] += t.hist[b];
-        wsum += t.wsum;
-        wmax = std::max(wmax, t.wmax);
-      }
-      // the open requests, with their windows, for the resolver
-      std::vector<Deferred> jobs;
-      size_t ndef = 0;
-      if (any_defer) {
-        for (Part& p : f.parts) {
-          if (!p.w->deferred()) continue;
-          Deferred d;
-          for (const Req& r : p.reqs)
-            if (is_deferred(r, *p.w)) d.reqs.push_back(r);
-          ndef += d.reqs.size();
-          d.w = std::move(p.w);
-          d.shard = p.shard;
-          jobs.push_back(std::move(d));
-        }
-      }
-      // recycle each part's window (unless the resolver has it) and request
-      // vector into its shard
-      for (Part& p : f.parts) {
-        if (p.w) p.w->reset();
-        p.reqs.clear();
-        Shard& sh = shards[p.shard];
-        std::lock_guard<std::mutex> g(sh.mu);
-        if (p.w && sh.spares.size() < kSpares) sh.spares.push_back(std::move(p.w));
-        if (sh.spare_reqs.size() < kSpares) sh.spare_reqs.push_back(std::move(p.reqs));
-      }
+      trace_slow(f, window_us);
+      const bool retried = recover(f.L);
+      const bool any_open = mark_open(f);
+      const WaitTally waits = run_callbacks(f, any_open);
+      std::vector<Part> jobs;
+      if (any_open) jobs = split_open(f);
+      for (Part& p : f.parts) shards[p.shard].recycle(p.w, &p.reqs);
       l.lock();
-      for (int b = 0; b < HB; b++) m_hist[b] += hist[b];
-      m_wait_sum += wsum;
-      m_wait_max = std::max(m_wait_max, wmax);
-      m_requests += nreq - ndef;
-      for (int k = 0; k < COA_QSTAGES; k++) m_stage_us[k] += (double)f.L.stage_ns[k] * 1e-3;
-      m_sig += f.L.nv + f.L.nhd + f.L.nvt;  // a message is one signature
-      m_hdr += f.L.nhd;
-      m_vote += f.L.nvt;
-      if (f.L.msg_route == Launch::MSG_LATENCY) m_msg_lat++;
-      if (f.L.msg_route == Launch::MSG_THROUGHPUT) m_msg_tp++;
-      m_batch += f.L.ng;
-      m_cert += f.L.nc;
-      m_dig += f.L.nd;
-      if (retried) {
-        m_retried++;
-        if (rc == COA_OK) m_recovered++;
-      }
-      if (window_us > m_window_us_max) {
-        m_window_us_max = window_us;
-        m_window_max_items = f.L.items();
-        m_window_max_kinds = f.L.kinds();
-        m_window_max_at_ms = (double)(f.t_launch - m_epoch_ns) * 1e-6;
-        m_window_max_dev_us = (double)f.L.stage_ns[COA_QSTAGE_DEVICE_WAIT] * 1e-3;
-      }
-      m_slot_wait_us_max = std::max(m_slot_wait_us_max, (double)f.L.slot_wait_ns * 1e-3);
-      if (rc != COA_OK) m_failed++;
+      m.record(f.L, f.t_launch, window_us, retried, waits);
       if (!jobs.empty()) {
         resolving += jobs.size();
-        for (Deferred& d : jobs) open.push_back(std::move(d));
+        for (Part& d : jobs) open.push_back(std::move(d));
         resolve_cv.notify_one();
       }
       busy--;
@@ -720,17 +595,124 @@ struct Lane {
     }
   }
 
+  // COA_QUEUE_TRACE_SLOW_US (diagnostics): a window slower than that, with
+  // its stages, on stderr.
+  void trace_slow(const Flight& f, double window_us) const {
+    if (!(trace_slow_us > 0 && window_us > trace_slow_us)) return;
+    const Launch& L = f.L;
+    fprintf(stderr,
+            "[coa queue] slow window %.0f us at t=%.6f s: %zu items kinds %u slot %d; slot_wait %.0f pack %.0f "
+            "enqueue %.0f (pin %.0f h2d %.0f launch %.0f d2h %.0f event %.0f) device_wait %.0f scatter %.0f us\n",
+            window_us, (double)f.t_launch * 1e-9, L.items(), L.kinds(), L.slot, L.stage_ns[COA_QSTAGE_SLOT_WAIT] * 1e-3,
+            L.stage_ns[COA_QSTAGE_PACK] * 1e-3, L.stage_ns[COA_QSTAGE_ENQUEUE] * 1e-3, L.enq_ns[Launch::ENQ_PIN] * 1e-3,
+            L.enq_ns[Launch::ENQ_H2D] * 1e-3, L.enq_ns[Launch::ENQ_LAUNCH] * 1e-3, L.enq_ns[Launch::ENQ_D2H] * 1e-3,
+            L.enq_ns[Launch::ENQ_EVENT] * 1e-3, L.stage_ns[COA_QSTAGE_DEVICE_WAIT] * 1e-3,
+            L.stage_ns[COA_QSTAGE_SCATTER] * 1e-3);
+  }
+
+  // A launch that failed on the device (a HIP error or an allocation
+  // failure; not "no device" or bad arguments): retried on the recovery
+  // context of each device in turn (the first retry on the next device),
+  // until one succeeds.  True if the launch had failed.
+  static bool recoverable(int rc) { return rc == COA_EHIP || rc == COA_ENOMEM; }
+  bool recover(Launch& L) {
+    if (!recoverable(L.rc)) return false;
+    const int n = std::max(1, be->devices());
+    for (int a = 1; a <= n && recoverable(L.rc); a++) {
+      L.reset_outputs();
+      L.attempts++;
+      be->retry(L, a);
+    }
+    return true;
+  }
+
+  // True if the backend left requests of the window open: those go to the
+  // resolver, the rest are answered now.  A failed window leaves nothing
+  // open: every request gets the error.
+  static bool mark_open(Flight& f) {
+    bool any = false;
+    for (Part& p : f.parts) {
+      if (f.L.rc != COA_OK) p.w->close_open();
+      any = any || p.w->deferred();
+    }
+    return any;
+  }
+
+  // The callbacks of the window's requests (not the open ones), in runs of
+  // contiguous requests -- the helpers join for large launches -- with the
+  // wait times from a clock read every 32 requests.
+  WaitTally run_callbacks(Flight& f, bool any_open) {
+    const int64_t tcb = now_ns();
+    const int rc = f.L.rc;
+    struct Run {
+      const Part* p;
+      size_t lo, hi;
+    };
+    std::vector<Run> runs;
+    size_t nreq = 0;
+    for (const Part& p : f.parts) {
+      for (size_t lo = 0; lo < p.reqs.size(); lo += kRun) runs.push_back({&p, lo, std::min(p.reqs.size(), lo + kRun)});
+      nreq += p.reqs.size();
+    }
+    std::vector<WaitTally> tallies(runs.size());
+    auto answer_run = [&](size_t ri) {
+      const Run& g = runs[ri];
+      const Window& w = *g.p->w;
+      WaitTally& t = tallies[ri];
+      int64_t tnow = now_ns();
+      for (size_t k = g.lo; k < g.hi; k++) {
+        const Req& r = g.p->reqs[k];
+        if (any_open && is_deferred(r, w)) continue;  // the resolver answers it
+        if (((k - g.lo) & 31) == 31) tnow = now_ns();
+        t.add((double)(tnow - r.t0) * 1e-3);
+        answer_req(r, w, rc);
+      }
+    };
+    if (n_helpers > 0 && nreq >= kParallelAnswer && runs.size() > 1) {
+      if (!helpers_on) {
+        helpers.start(n_helpers);
+        helpers_on = true;
+      }
+      helpers.run(runs.size(), answer_run);
+    } else {
+      for (size_t ri = 0; ri < runs.size(); ri++) answer_run(ri);
+    }
+    f.L.stage_ns[COA_QSTAGE_CALLBACKS] += now_ns() - tcb;
+    WaitTally all;
+    for (const WaitTally& t : tallies) all.merge(t);
+    return all;
+  }
+
+  // The open requests, with their windows (moved out of the flight), for the
+  // resolver.
+  static std::vector<Part> split_open(Flight& f) {
+    std::vector<Part> jobs;
+    for (Part& p : f.parts) {
+      if (!p.w->deferred()) continue;
+      Part d;
+      for (const Req& r : p.reqs)
+        if (is_deferred(r, *p.w)) d.reqs.push_back(r);
+      d.w = std::move(p.w);
+      d.shard = p.shard;
+      jobs.push_back(std::move(d));
+    }
+    return jobs;
+  }
+
   // The resolver: takes every deferred part queued so far, has the backend
   // decide them in one pass (one engine call per kind for all of them), and
   // answers their callbacks -- off the completion thread, so the windows
-  // behind an open certificate are answered while it is being decided.
+  // behind an open certificate are answered while it is being decided.  A
+  // pass that failed answers them with the engine error and "failed" values.
+  // The windows go back to their shards' pools (their request vectors were
+  // the completer's to recycle).
   void resolve_loop() {
     t_queue_thread = true;
     std::unique_lock<std::mutex> l(mu);
     for (;;) {
       resolve_cv.wait(l, [&] { return !open.empty() || resolver_stop; });
       if (open.empty()) return;
-      std::vector<Deferred> jobs;
+      std::vector<Part> jobs;
       while (!open.empty()) {
         jobs.push_back(std::move(open.front()));
         open.pop_front();
@@ -738,54 +720,21 @@ struct Lane {
       l.unlock();
       const int64_t t0 = now_ns();
       std::vector<Window*> ws;
-      for (Deferred& d : jobs) ws.push_back(d.w.get());
+      for (Part& d : jobs) ws.push_back(d.w.get());
       const int rc = be->resolve(ws);
-      if (rc != COA_OK) {
-        for (Window* w : ws) {  // "failed" outputs with the engine error
-          for (uint32_t c : w->c_defer) w->c_out[c] = 7;
-          for (uint32_t m : w->m_defer) (m < w->nhd ? w->hd_out[m] : w->vt_out[m - w->nhd]) = m < w->nhd ? 3 : 1;
-          if (w->g_defer) w->g_out.assign(w->ng, 1);
-        }
-      }
+      if (rc != COA_OK)
+        for (Window* w : ws) w->fail_open();
       const int64_t t1 = now_ns();
-      uint64_t hist[HB] = {};
-      double wsum = 0.0, wmax = 0.0;
-      size_t n = 0;
-      for (const Deferred& d : jobs) {
-        const Window& w = *d.w;
+      WaitTally waits;
+      for (const Part& d : jobs)
         for (const Req& r : d.reqs) {
-          const double us = (double)(now_ns() - r.t0) * 1e-3;
-          wsum += us;
-          wmax = std::max(wmax, us);
-          hist[wait_bucket(us)]++;
-          if (r.kind == K_CERT)
-            r.cb(r.user, rc, w.c_out.data() + r.idx, 1);
-          else if (r.kind == K_HEADER)
-            r.cb(r.user, rc, w.hd_out.data() + r.idx, 1);
-          else if (r.kind == K_VOTE)
-            r.cb(r.user, rc, w.vt_out.data() + r.idx, 1);
-          else
-            r.cb(r.user, rc, w.g_out.data() + r.idx, 1);
-          n++;
+          waits.add((double)(now_ns() - r.t0) * 1e-3);
+          answer_req(r, *d.w, rc);
         }
-      }
       const int64_t t2 = now_ns();
-      for (Deferred& d : jobs) {  // the answered windows back to their shards' pools
-        d.w->reset();
-        Shard& sh = shards[d.shard];
-        std::lock_guard<std::mutex> g(sh.mu);
-        if (sh.spares.size() < kSpares) sh.spares.push_back(std::move(d.w));
-      }
+      for (Part& d : jobs) shards[d.shard].recycle(d.w, nullptr);
       l.lock();
-      for (int b = 0; b < HB; b++) m_hist[b] += hist[b];
-      m_wait_sum += wsum;
-      m_wait_max = std::max(m_wait_max, wmax);
-      m_requests += n;
-      m_deferred += n;
-      m_passes++;
-      m_resolve_us_max = std::max(m_resolve_us_max, (double)(t1 - t0) * 1e-3);
-      m_stage_us[COA_QSTAGE_RESOLVE] += (double)(t1 - t0) * 1e-3;
-      m_stage_us[COA_QSTAGE_CALLBACKS] += (double)(t2 - t1) * 1e-3;
+      m.record_pass(waits, (double)(t1 - t0) * 1e-3, (double)(t2 - t1) * 1e-3);
       resolving -= jobs.size();
       if (idle()) idle_cv.notify_all();
     }
@@ -793,21 +742,8 @@ struct Lane {
 
   void reset_metrics() {
     std::lock_guard<std::mutex> l(mu);
-    m_requests = m_windows = m_sig = m_batch = m_cert = m_dig = 0;
-    m_max_window = m_max_in_flight = 0;
-    m_retried = m_recovered = m_failed = 0;
+    m = LaneMetrics{now_ns()};
     m_max_pending.store(0);
-    m_wait_sum = m_wait_max = 0.0;
-    std::fill(m_hist, m_hist + HB, 0);
-    m_window_us_max = m_slot_wait_us_max = 0.0;
-    m_window_max_items = 0;
-    m_window_max_kinds = 0;
-    m_epoch_ns = now_ns();
-    m_window_max_at_ms = m_window_max_dev_us = 0.0;
-    m_deferred = m_passes = 0;
-    m_hdr = m_vote = m_msg_lat = m_msg_tp = 0;
-    m_resolve_us_max = 0.0;
-    std::fill(m_stage_us, m_stage_us + COA_QSTAGES, 0.0);
     be->reset_grows();
   }
 
@@ -839,19 +775,6 @@ struct Lane {
   }
 };
 
-double hist_percentile(const uint64_t* hist, double q) {
-  uint64_t total = 0;
-  for (int b = 0; b < HB; b++) total += hist[b];
-  if (total == 0) return 0.0;
-  const double want = q * (double)total;
-  uint64_t run = 0;
-  for (int b = 0; b < HB; b++) {
-    run += hist[b];
-    if ((double)run >= want) return bucket_mid(b);
-  }
-  return bucket_mid(HB - 1);
-}
-
 }  // namespace
 
 struct coa_queue {
@@ -861,23 +784,69 @@ struct coa_queue {
 };
 
 namespace {
-void submitted(Lane* q, Shard& sh, std::unique_lock<std::mutex>& sl, Kind kind, uint32_t idx, uint32_t n,
-               coa_verdict_cb cb, void* user, size_t items, int64_t t_in) {
-  sh.reqs.push_back(Req{cb, user, t_in, idx, n, kind});
-  sh.w->intake_ns += now_ns() - t_in;
-  sh.items += items;
-  size_t delta = 0;
-  if (sh.reported == 0 || sh.items - sh.reported >= kReport) {
-    delta = sh.items - sh.reported;
-    sh.reported = sh.items;
+// A submission's intake: the request goes into the calling thread's shard of
+// the kind's lane under that shard's lock (held from the constructor to
+// done(), or to the destructor if the lane is stopping); then the lane's
+// pending count (and, on an edge, its collector) learns of it.
+struct Intake {
+  const int64_t t_in = now_ns();
+  Lane& ln;
+  std::unique_lock<std::mutex> sl;
+  Shard& sh;
+  Window& w;  // the shard's open window, its capacity reserved
+  Intake(coa_queue* q, Kind kind) : ln(q->lane_of(kind)), sh(ln.intake(sl)), w(*sh.w) {
+    if (ok() && !w.reserved) w.reserve_for(ln.reserve_items, ln.digest_lane);
   }
-  sl.unlock();
-  if (delta) q->arrived(delta);
-}
+  bool ok() const { return !ln.stop.load(); }
+  // The request is in the window as the kind's idx-th (n: a K_VERIFY
+  // request's signatures), `items` items more for the collector.
+  void done(Kind kind, uint32_t idx, uint32_t n, size_t items, coa_verdict_cb cb, void* user) {
+    sh.reqs.push_back(Req{cb, user, t_in, idx, n, kind});
+    w.intake_ns += now_ns() - t_in;
+    sh.items += items;
+    size_t delta = 0;
+    if (sh.reported == 0 || sh.items - sh.reported >= kReport) {
+      delta = sh.items - sh.reported;
+      sh.reported = sh.items;
+    }
+    sl.unlock();
+    if (delta) ln.arrived(delta);
+  }
+};
 
 template <size_t N>
 inline void put(std::vector<uint8_t>& v, const uint8_t* src) {
   v.insert(v.end(), src, src + N);  // one copy (resize would zero the bytes first)
+}
+
+// A certificate request: `r` holds the caller's pointers; a copy (r.owned)
+// appends their bytes to the window's own buffer, one append per
+// field, and keeps the offsets (bind() turns them into pointers at the take).
+inline int submit_cert(coa_queue* q, Window::CertRef r, coa_verdict_cb cb, void* user) {
+  if (!q || (r.hlen && !r.hdr) || !r.id || !r.origin || !r.hsig || (r.nv && (!r.vpks || !r.vsigs)) || !cb)
+    return COA_EINVAL;
+  Intake in(q, K_CERT);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
+  if (r.owned) {
+    std::vector<uint8_t>& o = w.c_own;
+    auto own = [&o](const uint8_t*& field, size_t len) {
+      const uint8_t* src = field;
+      field = reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(o.size()));
+      if (len) o.insert(o.end(), src, src + len);
+    };
+    own(r.hdr, r.hlen);
+    own(r.id, 32);
+    own(r.origin, 32);
+    own(r.hsig, 64);
+    own(r.vpks, r.nv * 32);
+    own(r.vsigs, r.nv * 64);
+  }
+  w.c_refs.push_back(r);
+  w.c_votes += r.nv;
+  w.c_hbytes += r.hlen;
+  in.done(K_CERT, (uint32_t)w.nc++, 1, 1 + r.nv, cb, user);
+  return COA_OK;
 }
 }  // namespace
 
@@ -932,54 +901,49 @@ coa_queue* coa_queue_create(size_t max_batch, uint32_t max_delay_us) {
   return q;
 }
 
-// The submissions: the request goes into the calling thread's shard of the
-// kind's lane under that shard's lock; then the lane's pending count (and, on
-// an edge, its collector) learns of it.
-#define COA_Q_INTAKE(q, kind)                                                \
-  const int64_t t_in = now_ns();                                             \
-  Lane* ln = &(q)->lane_of(kind);                                            \
-  std::unique_lock<std::mutex> sl;                                           \
-  Shard& sh = ln->intake(sl);                                                \
-  if (ln->stop.load()) return COA_EINVAL;                                    \
-  Window& w = *sh.w;                                                         \
-  if (!w.reserved) w.reserve_for(ln->reserve_items, ln->digest_lane);
-
-
+// The submissions (Intake above): arguments checked, the request's bytes
+// appended to the shard's window, done().
 int coa_queue_submit_verify(coa_queue* q, const uint8_t msg[32], const uint8_t pk[32], const uint8_t sig[64],
                             coa_verdict_cb cb, void* user) {
   if (!q || !msg || !pk || !sig || !cb) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_VERIFY)
+  Intake in(q, K_VERIFY);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   put<32>(w.v_msgs, msg);
   put<32>(w.v_pks, pk);
   put<64>(w.v_sigs, sig);
-  submitted(ln, sh, sl, K_VERIFY, (uint32_t)w.nv++, 1, cb, user, 1, t_in);
+  in.done(K_VERIFY, (uint32_t)w.nv++, 1, 1, cb, user);
   return COA_OK;
 }
 
 int coa_queue_submit_verify_many(coa_queue* q, const uint8_t* msgs, const uint8_t* pks, const uint8_t* sigs, size_t n,
                                  coa_verdict_cb cb, void* user) {
   if (!q || !cb || n == 0 || n > UINT32_MAX || !msgs || !pks || !sigs) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_VERIFY)
+  Intake in(q, K_VERIFY);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   w.v_msgs.insert(w.v_msgs.end(), msgs, msgs + n * 32);
   w.v_pks.insert(w.v_pks.end(), pks, pks + n * 32);
   w.v_sigs.insert(w.v_sigs.end(), sigs, sigs + n * 64);
   const uint32_t idx = (uint32_t)w.nv;
   w.nv += n;
-  submitted(ln, sh, sl, K_VERIFY, idx, (uint32_t)n, cb, user, n, t_in);
+  in.done(K_VERIFY, idx, (uint32_t)n, n, cb, user);
   return COA_OK;
 }
 
 int coa_queue_submit_batch(coa_queue* q, const uint8_t msg[32], const uint8_t* pks, const uint8_t* sigs, size_t n,
                            coa_verdict_cb cb, void* user) {
   if (!q || !msg || (n && (!pks || !sigs)) || !cb) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_BATCH)
+  Intake in(q, K_BATCH);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   put<32>(w.g_msgs, msg);
   if (n) {
     w.g_pks.insert(w.g_pks.end(), pks, pks + n * 32);
     w.g_sigs.insert(w.g_sigs.end(), sigs, sigs + n * 64);
   }
   w.g_offs.push_back(w.g_offs.back() + n);
-  submitted(ln, sh, sl, K_BATCH, (uint32_t)w.ng++, 1, cb, user, n ? n : 1, t_in);
+  in.done(K_BATCH, (uint32_t)w.ng++, 1, n ? n : 1, cb, user);
   return COA_OK;
 }
 
@@ -987,96 +951,56 @@ int coa_queue_submit_certificate(coa_queue* q, const uint8_t* header_data, size_
                                  const uint8_t origin[32], const uint8_t header_sig[64], uint64_t round,
                                  const uint8_t* vote_pks, const uint8_t* vote_sigs, size_t n_votes, coa_verdict_cb cb,
                                  void* user) {
-  if (!q || (header_len && !header_data) || !id || !origin || !header_sig || (n_votes && (!vote_pks || !vote_sigs)) ||
-      !cb)
-    return COA_EINVAL;
-  COA_Q_INTAKE(q, K_CERT)
-  // one append per field into the window's own buffer; the ref keeps offsets
-  // (bind() turns them into pointers at the take)
-  std::vector<uint8_t>& o = w.c_own;
-  auto at = [&o] { return reinterpret_cast<const uint8_t*>(static_cast<uintptr_t>(o.size())); };
-  Window::CertRef r;
-  r.hdr = at();
-  if (header_len) o.insert(o.end(), header_data, header_data + header_len);
-  r.id = at();
-  put<32>(o, id);
-  r.origin = at();
-  put<32>(o, origin);
-  r.hsig = at();
-  put<64>(o, header_sig);
-  r.vpks = at();
-  if (n_votes) o.insert(o.end(), vote_pks, vote_pks + n_votes * 32);
-  r.vsigs = at();
-  if (n_votes) o.insert(o.end(), vote_sigs, vote_sigs + n_votes * 64);
-  r.hlen = header_len;
-  r.round = round;
-  r.nv = n_votes;
-  r.owned = true;
-  w.c_refs.push_back(r);
-  w.c_votes += n_votes;
-  w.c_hbytes += header_len;
-  submitted(ln, sh, sl, K_CERT, (uint32_t)w.nc++, 1, cb, user, 1 + n_votes, t_in);
-  return COA_OK;
+  return submit_cert(q, {header_data, id, origin, header_sig, vote_pks, vote_sigs, header_len, round, n_votes, true},
+                     cb, user);
 }
 
 int coa_queue_submit_certificate_borrowed(coa_queue* q, const uint8_t* header_data, size_t header_len,
                                           const uint8_t id[32], const uint8_t origin[32], const uint8_t header_sig[64],
                                           uint64_t round, const uint8_t* vote_pks, const uint8_t* vote_sigs,
                                           size_t n_votes, coa_verdict_cb cb, void* user) {
-  if (!q || (header_len && !header_data) || !id || !origin || !header_sig || (n_votes && (!vote_pks || !vote_sigs)) ||
-      !cb)
-    return COA_EINVAL;
-  COA_Q_INTAKE(q, K_CERT)
-  Window::CertRef r;
-  r.hdr = header_data;
-  r.id = id;
-  r.origin = origin;
-  r.hsig = header_sig;
-  r.vpks = vote_pks;
-  r.vsigs = vote_sigs;
-  r.hlen = header_len;
-  r.round = round;
-  r.nv = n_votes;
-  r.owned = false;
-  w.c_refs.push_back(r);
-  w.c_votes += n_votes;
-  w.c_hbytes += header_len;
-  submitted(ln, sh, sl, K_CERT, (uint32_t)w.nc++, 1, cb, user, 1 + n_votes, t_in);
-  return COA_OK;
+  return submit_cert(q, {header_data, id, origin, header_sig, vote_pks, vote_sigs, header_len, round, n_votes, false},
+                     cb, user);
 }
 
 int coa_queue_submit_digest(coa_queue* q, const uint8_t* data, size_t len, coa_verdict_cb cb, void* user) {
   if (!q || (len && !data) || !cb) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_DIGEST)
+  Intake in(q, K_DIGEST);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   if (len) w.d_data.insert(w.d_data.end(), data, data + len);
   w.d_offs.push_back(w.d_data.size());
-  submitted(ln, sh, sl, K_DIGEST, (uint32_t)w.nd++, 1, cb, user, 1, t_in);
+  in.done(K_DIGEST, (uint32_t)w.nd++, 1, 1, cb, user);
   return COA_OK;
 }
 
 int coa_queue_submit_header(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
                             const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
   if (!q || (header_len && !header_data) || !id || !author || !sig || !cb) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_HEADER)
+  Intake in(q, K_HEADER);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   if (header_len) w.hd_data.insert(w.hd_data.end(), header_data, header_data + header_len);
   w.hd_offs.push_back(w.hd_data.size());
   put<32>(w.hd_ids, id);
   put<32>(w.hd_authors, author);
   put<64>(w.hd_sigs, sig);
-  submitted(ln, sh, sl, K_HEADER, (uint32_t)w.nhd++, 1, cb, user, 1, t_in);
+  in.done(K_HEADER, (uint32_t)w.nhd++, 1, 1, cb, user);
   return COA_OK;
 }
 
 int coa_queue_submit_vote(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
                           const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
   if (!q || !id || !origin || !author || !sig || !cb) return COA_EINVAL;
-  COA_Q_INTAKE(q, K_VOTE)
+  Intake in(q, K_VOTE);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
   put<32>(w.vt_ids, id);
   w.vt_rounds.push_back(round);
   put<32>(w.vt_origins, origin);
   put<32>(w.vt_authors, author);
   put<64>(w.vt_sigs, sig);
-  submitted(ln, sh, sl, K_VOTE, (uint32_t)w.nvt++, 1, cb, user, 1, t_in);
+  in.done(K_VOTE, (uint32_t)w.nvt++, 1, 1, cb, user);
   return COA_OK;
 }
 
@@ -1085,10 +1009,10 @@ int coa_queue_message_stats(coa_queue* q, uint64_t* headers, uint64_t* votes, ui
   if (!q) return COA_EINVAL;
   Lane& L = q->lanes[coa_q::LANE_VERIFY];
   std::lock_guard<std::mutex> l(L.mu);
-  if (headers) *headers = L.m_hdr;
-  if (votes) *votes = L.m_vote;
-  if (latency_windows) *latency_windows = L.m_msg_lat;
-  if (throughput_windows) *throughput_windows = L.m_msg_tp;
+  if (headers) *headers = L.m.hdr;
+  if (votes) *votes = L.m.vote;
+  if (latency_windows) *latency_windows = L.m.msg_lat;
+  if (throughput_windows) *throughput_windows = L.m.msg_tp;
   return COA_OK;
 }
 
@@ -1113,9 +1037,9 @@ int coa_queue_stats(coa_queue* q, uint64_t* launches, uint64_t* items, uint64_t*
   uint64_t w = 0, it = 0, g = 0;
   for (Lane& L : q->lanes) {
     std::lock_guard<std::mutex> l(L.mu);
-    w += L.m_windows;
-    it += L.m_sig;
-    g += L.m_batch + L.m_cert;
+    w += L.m.windows;
+    it += L.m.sig;
+    g += L.m.batch + L.m.cert;
   }
   if (launches) *launches = w;
   if (items) *items = it;
@@ -1127,52 +1051,27 @@ int coa_queue_digest_count(coa_queue* q, uint64_t* digests) {
   if (!q || !digests) return COA_EINVAL;
   Lane& L = q->lanes[coa_q::LANE_DIGEST];
   std::lock_guard<std::mutex> l(L.mu);
-  *digests = L.m_dig;
+  *digests = L.m.dig;
   return COA_OK;
 }
 
 int coa_queue_metrics(coa_queue* q, coa_queue_metrics_t* out) {
   if (!q || !out) return COA_EINVAL;
   std::memset(out, 0, sizeof(*out));
-  uint64_t hist[HB] = {};
-  double wsum = 0.0;
+  WaitTally waits;  // over all lanes
   for (int k = 0; k < coa_q::LANES; k++) {
     Lane& L = q->lanes[k];
     std::lock_guard<std::mutex> l(L.mu);
-    out->requests += L.m_requests;
-    out->windows += L.m_windows;
-    out->signatures += L.m_sig;
-    out->batches += L.m_batch;
-    out->certificates += L.m_cert;
-    out->digests += L.m_dig;
-    out->max_window = std::max<uint64_t>(out->max_window, L.m_max_window);
-    out->max_in_flight = std::max<uint64_t>(out->max_in_flight, L.m_max_in_flight);
+    L.m.add_to(*out, waits);
     out->max_pending = std::max<uint64_t>(out->max_pending, (uint64_t)std::max<int64_t>(0, L.m_max_pending.load()));
-    for (int b = 0; b < HB; b++) hist[b] += L.m_hist[b];
-    wsum += L.m_wait_sum;
-    out->wait_us_max = std::max(out->wait_us_max, L.m_wait_max);
-    out->retried_windows += L.m_retried;
-    out->recovered_windows += L.m_recovered;
-    out->failed_windows += L.m_failed;
-    if (L.m_window_us_max > out->window_us_max) {
-      out->window_us_max = L.m_window_us_max;
-      out->window_max_items = L.m_window_max_items;
-      out->window_max_kinds = L.m_window_max_kinds;
-      out->window_max_at_ms = L.m_window_max_at_ms;
-      out->window_max_device_us = L.m_window_max_dev_us;
-    }
-    out->slot_wait_us_max = std::max(out->slot_wait_us_max, L.m_slot_wait_us_max);
     out->staging_grows += L.be->grows();
     out->stream_kind = std::max(out->stream_kind, (int32_t)L.be->stream_kind());
     (k == coa_q::LANE_DIGEST ? out->slots_digest : out->slots_verify) = (uint32_t)L.be->slots();
-    out->deferred_requests += L.m_deferred;
-    out->resolver_passes += L.m_passes;
-    out->resolve_us_max = std::max(out->resolve_us_max, L.m_resolve_us_max);
-    for (int s = 0; s < COA_QSTAGES; s++) out->stage_us[s] += L.m_stage_us[s];
   }
-  out->wait_us_mean = out->requests ? wsum / (double)out->requests : 0.0;
-  out->wait_us_p50 = hist_percentile(hist, 0.50);
-  out->wait_us_p99 = hist_percentile(hist, 0.99);
+  out->wait_us_mean = out->requests ? waits.sum / (double)out->requests : 0.0;
+  out->wait_us_max = waits.max;
+  out->wait_us_p50 = coa_q::hist_percentile(waits.hist, 0.50);
+  out->wait_us_p99 = coa_q::hist_percentile(waits.hist, 0.99);
   return COA_OK;
 }
 

@@ -14,6 +14,13 @@
 
 namespace coa_q {
 
+// The "failed" value of each output kind: what a request's callback gets
+// with an engine error (a window whose every attempt failed, a resolver pass
+// that failed).  Digests are zero bytes.
+constexpr uint8_t kVerdictErr = 1;  // signatures, bare vote batches, whole votes
+constexpr uint8_t kCertFailed = COA_CERT_BAD_HEADER_ID | COA_CERT_BAD_HEADER_SIG | COA_CERT_BAD_VOTES;
+constexpr uint8_t kHeaderFailed = COA_CERT_BAD_HEADER_ID | COA_CERT_BAD_HEADER_SIG;
+
 // One intake shard's requests, packed contiguously by kind (the arrays the
 // engine's batched entry points take).  A launch takes the windows of every
 // shard that had requests (its "parts") and the backend packs them straight
@@ -94,16 +101,33 @@ struct Window {
   // Outputs sized and set to "failed" (verdict Err, all certificate bits,
   // zero digests) before a launch or a retry.
   void reset_outputs() {
-    v_out.assign(nv, 1);
-    g_out.assign(ng, 1);
-    c_out.assign(nc, 7);
+    v_out.assign(nv, kVerdictErr);
+    g_out.assign(ng, kVerdictErr);
+    c_out.assign(nc, kCertFailed);
     d_out.assign(nd * 32, 0);
-    hd_out.assign(nhd, 3);
-    vt_out.assign(nvt, 1);
+    hd_out.assign(nhd, kHeaderFailed);
+    vt_out.assign(nvt, kVerdictErr);
     c_raw.clear();
+    close_open();
+  }
+  // Nothing is left open any more: a failed window, whose every request gets
+  // the engine error from the completer.
+  void close_open() {
     c_defer.clear();
     m_defer.clear();
     g_defer = false;
+  }
+  // "Failed" outputs for exactly the requests left open (a resolver pass that
+  // failed: whatever it wrote is overwritten, the other outputs stay).
+  void fail_open() {
+    for (uint32_t c : c_defer) c_out[c] = kCertFailed;
+    for (uint32_t m : m_defer) {
+      if (m < nhd)
+        hd_out[m] = kHeaderFailed;
+      else
+        vt_out[m - nhd] = kVerdictErr;
+    }
+    if (g_defer) g_out.assign(ng, kVerdictErr);
   }
   // Capacity for the largest window the lane's collector closes (`items` =
   // twice max_batch: whole shards are taken until max_batch items are in),
@@ -137,10 +161,8 @@ struct Window {
   void reset() {
     nv = ng = nc = nd = nhd = nvt = 0;
     intake_ns = 0;
-    g_defer = false;
     c_raw.clear();
-    c_defer.clear();
-    m_defer.clear();
+    close_open();
     for (auto* v : {&hd_data, &hd_ids, &hd_authors, &hd_sigs, &hd_out, &vt_ids, &vt_origins, &vt_authors, &vt_sigs,
                     &vt_out})
       v->clear();
