@@ -600,6 +600,66 @@ int coa_queue_submit_vote(coa_queue* q, const uint8_t id[32], uint64_t round, co
  * or the last coa_queue_metrics_reset (any pointer may be null). */
 int coa_queue_message_stats(coa_queue* q, uint64_t* headers, uint64_t* votes, uint64_t* latency_windows,
                             uint64_t* throughput_windows);
+/* Verdict requests: the reference's whole DagResult of Certificate::verify /
+ * Header::verify / Vote::verify, decided in the window that carries the
+ * request.  The arguments are those of the crypto requests above plus
+ * payload_count (the header's payload entries, as in the *_verdict_many
+ * calls); the callback receives n = 4, one little-endian uint32_t verdict
+ * word (COA_DAG_*), with exactly the meaning of coa_certificate_verdict_many /
+ * coa_header_verdict_many / coa_vote_verdict_many and never
+ * COA_DAG_VOTES_OPEN.  A payload_count with 40 + 36 * count > header_len is
+ * refused at submission with COA_EINVAL.
+ *   - The committee must have been registered with
+ *     coa_committee_register_authorities.  A window pins its key-cache
+ *     generation and reads that generation's protocol table; if it has none
+ *     (plain coa_committee_register, or no registration), the window's verdict
+ *     requests are answered with status COA_EINVAL and the word
+ *     COA_DAG_INVALID_SIGNATURE.  That is no engine failure: nothing is
+ *     retried, no failure counter moves, and the rest of the window is
+ *     answered as usual.
+ *   - With a negative status (an engine error, or COA_EINVAL as above) the
+ *     word is COA_DAG_INVALID_SIGNATURE.
+ *   - Who answers: an item whose author or a voter is outside the committee
+ *     is answered by the protocol word alone, in its window -- it never goes
+ *     to the resolver thread.  Only a certificate whose every earlier check
+ *     passed and whose votes need the exact check (COA_DAG_VOTES_OPEN on the
+ *     device) is left to the resolver, which answers COA_DAG_INVALID_VOTES or
+ *     COA_DAG_OK.
+ *   - Verdict requests live on the verdict lane and share windows, intake
+ *     shards, slots, retry and ordering rules with the crypto requests; a
+ *     window may mix both, and the crypto requests' answers and routes are
+ *     what they are without them.  A header or vote verdict request counts one
+ *     item towards max_batch and one signature in coa_queue_stats /
+ *     coa_queue_metrics; a certificate verdict request counts as a
+ *     certificate request does.
+ *   - One kernel (k_window_verdict) after the window's crypto launches
+ *     decides the protocol checks of all its certificates, headers and votes
+ *     and merges them with the crypto status words; its words come back with
+ *     the window's one device-to-host copy.  A window that holds a verdict
+ *     request takes the staged route -- except a window of header and vote
+ *     verdicts alone of at most COA_QUEUE_MSG_LAT_MAX messages: the message
+ *     latency kernel decides their protocol checks itself (k_msg_verdict_lat),
+ *     on the routes of the crypto messages (alone and at most 64: the words
+ *     published, no copy back) and with no further launch.
+ * coa_queue_verdict_stats: verdict requests answered by kind and the windows
+ * that held one, since creation or the last coa_queue_metrics_reset (any
+ * pointer may be null).  No reference counterpart. */
+int coa_queue_submit_certificate_verdict(coa_queue* q, const uint8_t* header_data, size_t header_len,
+                                         const uint8_t id[32], const uint8_t origin[32], const uint8_t header_sig[64],
+                                         uint64_t round, const uint8_t* vote_pks, const uint8_t* vote_sigs,
+                                         size_t n_votes, uint32_t payload_count, coa_verdict_cb cb, void* user);
+int coa_queue_submit_certificate_verdict_borrowed(coa_queue* q, const uint8_t* header_data, size_t header_len,
+                                                  const uint8_t id[32], const uint8_t origin[32],
+                                                  const uint8_t header_sig[64], uint64_t round,
+                                                  const uint8_t* vote_pks, const uint8_t* vote_sigs, size_t n_votes,
+                                                  uint32_t payload_count, coa_verdict_cb cb, void* user);
+int coa_queue_submit_header_verdict(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
+                                    const uint8_t author[32], const uint8_t sig[64], uint32_t payload_count,
+                                    coa_verdict_cb cb, void* user);
+int coa_queue_submit_vote_verdict(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
+                                  const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user);
+int coa_queue_verdict_stats(coa_queue* q, uint64_t* certificates, uint64_t* headers, uint64_t* votes,
+                            uint64_t* verdict_windows);
 int coa_queue_flush(coa_queue* q);
 /* Window policy (no reference counterpart): with windows_in_flight = k > 0 a
  * window also closes at once while fewer than k windows are in flight, so a

@@ -312,6 +312,24 @@ extern "C" {
                                  sig: *const u8, cb: CoaVerdictCb, user: *mut c_void) -> c_int;
     pub fn coa_queue_message_stats(q: *mut CoaQueue, headers: *mut u64, votes: *mut u64, latency_windows: *mut u64,
                                    throughput_windows: *mut u64) -> c_int;
+    // verdict requests: the callback gets n = 4, one little-endian COA_DAG_* word
+    pub fn coa_queue_submit_certificate_verdict(q: *mut CoaQueue, header_data: *const u8, header_len: usize,
+                                                id: *const u8, origin: *const u8, header_sig: *const u8, round: u64,
+                                                vote_pks: *const u8, vote_sigs: *const u8, n_votes: usize,
+                                                payload_count: u32, cb: CoaVerdictCb, user: *mut c_void) -> c_int;
+    pub fn coa_queue_submit_certificate_verdict_borrowed(q: *mut CoaQueue, header_data: *const u8, header_len: usize,
+                                                         id: *const u8, origin: *const u8, header_sig: *const u8,
+                                                         round: u64, vote_pks: *const u8, vote_sigs: *const u8,
+                                                         n_votes: usize, payload_count: u32, cb: CoaVerdictCb,
+                                                         user: *mut c_void) -> c_int;
+    pub fn coa_queue_submit_header_verdict(q: *mut CoaQueue, header_data: *const u8, header_len: usize, id: *const u8,
+                                           author: *const u8, sig: *const u8, payload_count: u32, cb: CoaVerdictCb,
+                                           user: *mut c_void) -> c_int;
+    pub fn coa_queue_submit_vote_verdict(q: *mut CoaQueue, id: *const u8, round: u64, origin: *const u8,
+                                         author: *const u8, sig: *const u8, cb: CoaVerdictCb, user: *mut c_void)
+                                         -> c_int;
+    pub fn coa_queue_verdict_stats(q: *mut CoaQueue, certificates: *mut u64, headers: *mut u64, votes: *mut u64,
+                                   verdict_windows: *mut u64) -> c_int;
     pub fn coa_queue_flush(q: *mut CoaQueue) -> c_int;
     pub fn coa_queue_set_idle_launch(q: *mut CoaQueue, windows_in_flight: u32) -> c_int;
     pub fn coa_queue_stats(q: *mut CoaQueue, launches: *mut u64, items: *mut u64, groups: *mut u64) -> c_int;

@@ -13,7 +13,13 @@
 //!     verdicts out to the requests' oneshot senders;
 //!   * vote batches (`Signature::verify_batch`, :206-219), whole certificates
 //!     (the fused `Certificate::verify` crypto, messages.rs:189-215) and
-//!     worker batch digests (worker/src/processor.rs:38) go one request each.
+//!     worker batch digests (worker/src/processor.rs:38) go one request each;
+//!   * whole verdicts (`certificate_verdict`, `header_verdict`,
+//!     `vote_verdict`): the reference's DagResult of Certificate::verify /
+//!     Header::verify / Vote::verify as one COA_DAG_* word, decided in the
+//!     request's window against the committee of
+//!     `coa_committee_register_authorities` (the `coa_queue_submit_*_verdict`
+//!     requests), one request each.
 //!
 //! The engine answers on its completion thread through the `extern "C"`
 //! callbacks below; each one takes back the boxed sender(s) it was given and
@@ -142,7 +148,38 @@ type CertificateReply = Result<(u8, CertificateCrypto), (c_int, CertificateCrypt
 /// handed back (for the CPU answer: no copy kept on the success path).
 type BatchReply = Result<Result<(), CryptoError>, (c_int, Vec<(PublicKey, [u8; 64])>)>;
 
+/// A verdict request's COA_DAG_* word -- or the engine's negative status
+/// (COA_EINVAL: the window's committee generation has no protocol table, i.e.
+/// the committee was not registered with its stakes).
+type WordReply = Result<u32, c_int>;
+
+/// A certificate's verdict word with its crypto handed back, as
+/// `CertificateReply`.
+type CertificateWordReply = Result<(u32, CertificateCrypto), (c_int, CertificateCrypto)>;
+
+/// One header for `Header::verify`'s verdict: the bytes `Header::digest`
+/// hashes, its payload entries, id, author and signature.
+pub struct HeaderMessage {
+    pub header_input: Vec<u8>,
+    pub payload_count: u32,
+    pub id: Digest,
+    pub author: PublicKey,
+    pub signature: [u8; 64],
+}
+
+/// One vote for `Vote::verify`'s verdict.
+pub struct VoteMessage {
+    pub id: Digest,
+    pub round: u64,
+    pub origin: PublicKey,
+    pub author: PublicKey,
+    pub signature: [u8; 64],
+}
+
 enum Request {
+    CertificateVerdict(CertificateCrypto, u32, oneshot::Sender<CertificateWordReply>),
+    HeaderVerdict(HeaderMessage, oneshot::Sender<WordReply>),
+    VoteVerdict(VoteMessage, oneshot::Sender<WordReply>),
     Verify(Digest, PublicKey, [u8; 64], oneshot::Sender<Verdict>),
     Batch(Digest, Vec<(PublicKey, [u8; 64])>, oneshot::Sender<BatchReply>),
     Certificate(CertificateCrypto, oneshot::Sender<CertificateReply>),
@@ -261,6 +298,37 @@ impl VerifyService {
         }
     }
 
+    /// `Certificate::verify`'s whole verdict (primary/src/messages.rs:189-215)
+    /// as the COA_DAG_* word of `coa_certificate_verdict_many`, with the
+    /// request handed back; `payload_count` is the header's payload entries.
+    /// `Err`: the engine's status (nothing on the CPU path knows the
+    /// committee's stakes, so the caller decides).
+    pub async fn certificate_verdict(&self, crypto: CertificateCrypto, payload_count: u32)
+                                     -> (Result<u32, c_int>, CertificateCrypto) {
+        let (sender, receiver) = oneshot::channel();
+        self.send(Request::CertificateVerdict(crypto, payload_count, sender)).await;
+        match receiver.await.expect("Failed to receive verdict word from Verify Service") {
+            Ok((word, c)) => (Ok(word), c),
+            Err((status, c)) => (Err(status), c),
+        }
+    }
+
+    /// `Header::verify`'s whole verdict (primary/src/messages.rs:48-67) as the
+    /// COA_DAG_* word of `coa_header_verdict_many`.
+    pub async fn header_verdict(&self, header: HeaderMessage) -> Result<u32, c_int> {
+        let (sender, receiver) = oneshot::channel();
+        self.send(Request::HeaderVerdict(header, sender)).await;
+        receiver.await.expect("Failed to receive verdict word from Verify Service")
+    }
+
+    /// `Vote::verify`'s whole verdict (primary/src/messages.rs:131-142) as the
+    /// COA_DAG_* word of `coa_vote_verdict_many`.
+    pub async fn vote_verdict(&self, vote: VoteMessage) -> Result<u32, c_int> {
+        let (sender, receiver) = oneshot::channel();
+        self.send(Request::VoteVerdict(vote, sender)).await;
+        receiver.await.expect("Failed to receive verdict word from Verify Service")
+    }
+
     /// `Digest(Sha512(bytes)[..32])` (worker/src/processor.rs:38), with the
     /// bytes handed back (the queue copies them at submission; no clone).
     pub async fn digest(&self, bytes: Vec<u8>) -> (Digest, Vec<u8>) {
@@ -299,6 +367,9 @@ fn submit_window(queue: &Queue, window: Vec<Request>) {
             Request::Batch(digest, votes, sender) => submit_batch(queue, &digest, votes, sender),
             Request::Certificate(crypto, sender) => submit_certificate(queue, crypto, sender),
             Request::Digest(bytes, sender) => submit_digest(queue, bytes, sender),
+            Request::CertificateVerdict(crypto, count, sender) => submit_certificate_verdict(queue, crypto, count, sender),
+            Request::HeaderVerdict(header, sender) => submit_header_verdict(queue, header, sender),
+            Request::VoteVerdict(vote, sender) => submit_vote_verdict(queue, vote, sender),
         }
     }
     if senders.is_empty() {
@@ -376,6 +447,58 @@ fn submit_digest(queue: &Queue, bytes: Vec<u8>, sender: oneshot::Sender<DigestRe
     }
 }
 
+// The verdict requests box what rides along through `give` and take it back
+// through `take`: once in the callback, or once in the submit-failure branch.
+fn give<T>(value: T) -> *mut c_void {
+    Box::into_raw(Box::new(value)) as *mut c_void
+}
+unsafe fn take<T>(user: *mut c_void) -> T {
+    *Box::from_raw(user.cast::<T>())
+}
+
+fn submit_certificate_verdict(queue: &Queue, crypto: CertificateCrypto, payload_count: u32,
+                              sender: oneshot::Sender<CertificateWordReply>) {
+    // borrowed, as submit_certificate: the boxed request is read in place
+    let boxed = give((sender, crypto));
+    let c = unsafe { &(*(boxed as *const (oneshot::Sender<CertificateWordReply>, CertificateCrypto))).1 };
+    let rc = unsafe {
+        ffi::coa_queue_submit_certificate_verdict_borrowed(queue.0, c.header_input().as_ptr(), c.header_input().len(),
+                                          c.id().as_ptr(), c.origin().as_ptr(), c.header_signature().as_ptr(),
+                                          c.round(), c.vote_keys().as_ptr(), c.vote_signatures().as_ptr(),
+                                          c.n_votes(), payload_count, Some(on_certificate_word), boxed)
+    };
+    if rc != ffi::COA_OK {
+        let (sender, crypto) = unsafe { take::<(oneshot::Sender<CertificateWordReply>, CertificateCrypto)>(boxed) };
+        let _ = sender.send(Err((rc, crypto)));
+    }
+}
+
+fn submit_header_verdict(queue: &Queue, header: HeaderMessage, sender: oneshot::Sender<WordReply>) {
+    // copied at submission: only the sender rides along
+    let boxed = give(sender);
+    let rc = unsafe {
+        ffi::coa_queue_submit_header_verdict(queue.0, header.header_input.as_ptr(), header.header_input.len(),
+                                             header.id.0.as_ptr(), header.author.0.as_ptr(),
+                                             header.signature.as_ptr(), header.payload_count, Some(on_word), boxed)
+    };
+    if rc != ffi::COA_OK {
+        let sender = unsafe { take::<oneshot::Sender<WordReply>>(boxed) };
+        let _ = sender.send(Err(rc));
+    }
+}
+
+fn submit_vote_verdict(queue: &Queue, vote: VoteMessage, sender: oneshot::Sender<WordReply>) {
+    let boxed = give(sender);
+    let rc = unsafe {
+        ffi::coa_queue_submit_vote_verdict(queue.0, vote.id.0.as_ptr(), vote.round, vote.origin.0.as_ptr(),
+                                           vote.author.0.as_ptr(), vote.signature.as_ptr(), Some(on_word), boxed)
+    };
+    if rc != ffi::COA_OK {
+        let sender = unsafe { take::<oneshot::Sender<WordReply>>(boxed) };
+        let _ = sender.send(Err(rc));
+    }
+}
+
 // ------------------------------------------------------------- callbacks
 // coa_verdict_cb: void (*)(void* user, int status, const uint8_t* verdicts,
 // size_t n).  Each runs exactly once per queued request, on the engine's
@@ -439,6 +562,38 @@ unsafe extern "C" fn on_digest(user: *mut c_void, status: c_int, verdicts: *cons
         let mut digest = [0u8; 32];
         digest.copy_from_slice(std::slice::from_raw_parts(verdicts, 32));
         Ok((Digest(digest), bytes))
+    };
+    let _ = sender.send(reply);
+}
+
+/// The four bytes of a verdict request's answer: one little-endian word.
+unsafe fn word_of(verdicts: *const u8, n: usize) -> Option<u32> {
+    if verdicts.is_null() || n != 4 {
+        return None;
+    }
+    let mut le = [0u8; 4];
+    le.copy_from_slice(std::slice::from_raw_parts(verdicts, 4));
+    Some(u32::from_le_bytes(le))
+}
+
+/// One header or vote verdict: the COA_DAG_* word.
+unsafe extern "C" fn on_word(user: *mut c_void, status: c_int, verdicts: *const u8, n: usize) {
+    let sender = take::<oneshot::Sender<WordReply>>(user);
+    let reply = match word_of(verdicts, n) {
+        _ if status != ffi::COA_OK => Err(status),
+        Some(word) => Ok(word),
+        None => Err(ffi::COA_EINVAL),
+    };
+    let _ = sender.send(reply);
+}
+
+/// One certificate verdict: the COA_DAG_* word, and the request handed back.
+unsafe extern "C" fn on_certificate_word(user: *mut c_void, status: c_int, verdicts: *const u8, n: usize) {
+    let (sender, crypto) = take::<(oneshot::Sender<CertificateWordReply>, CertificateCrypto)>(user);
+    let reply = match word_of(verdicts, n) {
+        _ if status != ffi::COA_OK => Err((status, crypto)),
+        Some(word) => Ok((word, crypto)),
+        None => Err((ffi::COA_EINVAL, crypto)),
     };
     let _ = sender.send(reply);
 }

@@ -526,3 +526,255 @@ int latc_queue_messages(coa_queue* q, int route, int votes, int producers, int r
   if (atomic_load(&answered) != (long)(n * (size_t)rounds)) atomic_fetch_add(&wrong, 1);
   return atomic_load(&wrong);
 }
+
+/* Headers or votes as whole-verdict requests against crypto requests
+ * (tools/queue_verdict_ab.py).  route 0: coa_queue_submit_header_verdict /
+ * coa_queue_submit_vote_verdict, each callback's word compared with
+ * expect_words[k].  route 1: the crypto requests (coa_queue_submit_header /
+ * coa_queue_submit_vote), their bytes kept, and after the flush ONE host
+ * thread (the caller) runs the protocol checks of Header::verify /
+ * Vote::verify for all n -- the author's stake by binary search over the
+ * committee keys (sorted bytewise), a header's worker ids by binary search
+ * over the author's sorted ids -- and merges them with the crypto byte into
+ * the word, compared likewise; that part's time into *host_check_s (it is
+ * inside *elapsed_s).  Returns the number of wrong, failed or missing answers. */
+typedef struct {
+  const uint32_t* expect_word; /* route 0 */
+  uint8_t* got;                /* route 1: where the crypto byte goes */
+  atomic_int* wrong;
+  atomic_long* answered;
+} VerdictReq;
+
+typedef struct {
+  coa_queue* q;
+  int route, votes, p, producers;
+  double rate, t0_us;
+  size_t n;
+  const uint8_t *hdata, *ids, *origins, *authors, *sigs;
+  const uint64_t *hoff, *rounds_of;
+  const uint32_t *pcounts, *expect;
+  uint8_t* got;
+  atomic_int* wrong;
+  atomic_long* answered;
+} VerdictJob;
+
+static void verdict_cb(void* user, int status, const uint8_t* v, size_t n) {
+  VerdictReq* r = (VerdictReq*)user;
+  if (r->got) {
+    if (status != COA_OK || n != 1 || !v) atomic_fetch_add(r->wrong, 1);
+    else *r->got = v[0];
+  } else {
+    uint32_t w = 0xffffffffu;
+    if (v && n == 4) memcpy(&w, v, 4);
+    if (status != COA_OK || w != *r->expect_word) atomic_fetch_add(r->wrong, 1);
+  }
+  atomic_fetch_add(r->answered, 1);
+  free(r);
+}
+
+static void* verdict_thread(void* arg) {
+  VerdictJob* j = (VerdictJob*)arg;
+  size_t sent = 0;
+  for (size_t k = (size_t)j->p; k < j->n; k += (size_t)j->producers, sent++) {
+    if (j->rate > 0) {
+      const double due = j->t0_us + (double)sent * 1e6 / j->rate;
+      for (;;) {
+        const double left = due - now_us();
+        if (left <= 0) break;
+        if (left > 300.0) {
+          struct timespec ts = {0, (long)((left - 150.0) * 1e3)};
+          nanosleep(&ts, NULL);
+        }
+      }
+    }
+    VerdictReq* m = (VerdictReq*)malloc(sizeof(VerdictReq));
+    m->expect_word = j->expect + k;
+    m->got = j->route ? j->got + k : NULL;
+    m->wrong = j->wrong;
+    m->answered = j->answered;
+    const uint8_t* hdr = j->hdata + j->hoff[k];
+    const size_t hlen = (size_t)(j->hoff[k + 1] - j->hoff[k]);
+    int rc;
+    if (j->votes)
+      rc = (j->route ? coa_queue_submit_vote : coa_queue_submit_vote_verdict)(
+          j->q, j->ids + 32 * k, j->rounds_of[k], j->origins + 32 * k, j->authors + 32 * k, j->sigs + 64 * k,
+          verdict_cb, m);
+    else if (j->route)
+      rc = coa_queue_submit_header(j->q, hdr, hlen, j->ids + 32 * k, j->authors + 32 * k, j->sigs + 64 * k, verdict_cb, m);
+    else
+      rc = coa_queue_submit_header_verdict(j->q, hdr, hlen, j->ids + 32 * k, j->authors + 32 * k, j->sigs + 64 * k,
+                                           j->pcounts[k], verdict_cb, m);
+    if (rc != COA_OK) {
+      atomic_fetch_add(j->wrong, 1);
+      atomic_fetch_add(j->answered, 1);
+      free(m);
+    }
+  }
+  return NULL;
+}
+
+int latc_queue_verdict_messages(coa_queue* q, int route, int votes, int producers, double rate_per_s,
+                                const uint8_t* hdata, const uint64_t* hoff, const uint8_t* ids,
+                                const uint64_t* rounds_of, const uint8_t* origins, const uint8_t* authors,
+                                const uint8_t* sigs, const uint32_t* pcounts, size_t n, const uint32_t* expect_words,
+                                const uint8_t* sorted_keys, const uint32_t* stakes, const uint64_t* woff,
+                                const uint32_t* wids, size_t nk, double* elapsed_s, double* host_check_s) {
+  if (!q || producers < 1 || producers > 64) return -1;
+  atomic_int wrong = 0;
+  atomic_long answered = 0;
+  uint8_t* got = (uint8_t*)malloc(n + 1);
+  if (!got) return -1;
+  memset(got, 0xff, n + 1);
+  VerdictJob jobs[64];
+  pthread_t th[64];
+  const double t0 = now_us();
+  for (int p = 0; p < producers; p++) {
+    VerdictJob j = {q, route, votes, p, producers, rate_per_s / producers, t0, n, hdata, ids, origins, authors, sigs,
+                    hoff, rounds_of, pcounts, expect_words, got, &wrong, &answered};
+    jobs[p] = j;
+  }
+  for (int p = 0; p < producers; p++) pthread_create(&th[p], NULL, verdict_thread, &jobs[p]);
+  for (int p = 0; p < producers; p++) pthread_join(th[p], NULL);
+  coa_queue_flush(q);
+  *host_check_s = 0;
+  if (route) { /* the protocol checks and the merge, one host thread */
+    const double t1 = now_us();
+    for (size_t k = 0; k < n; k++) {
+      size_t lo = 0, hi = nk;
+      long slot = -1;
+      while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        const int c = memcmp(sorted_keys + 32 * mid, authors + 32 * k, 32);
+        if (c == 0) {
+          slot = (long)mid;
+          break;
+        }
+        if (c < 0) lo = mid + 1;
+        else hi = mid;
+      }
+      uint32_t proto = 0;
+      if (slot < 0 || stakes[slot] == 0) {
+        proto = COA_DAG_UNKNOWN_AUTHOR;
+      } else if (!votes) {
+        const uint8_t* hdr = hdata + hoff[k];
+        for (uint32_t e = 0; e < pcounts[k] && !proto; e++) {
+          uint32_t id;
+          memcpy(&id, hdr + 40 + 36 * (size_t)e + 32, 4);
+          uint64_t a = woff[slot], b = woff[slot + 1];
+          int found = 0;
+          while (a < b && !found) {
+            const uint64_t mid = (a + b) / 2;
+            if (wids[mid] == id) found = 1;
+            else if (wids[mid] < id) a = mid + 1;
+            else b = mid;
+          }
+          if (!found) proto = COA_DAG_MALFORMED_HEADER;
+        }
+      }
+      const uint8_t b = got[k];
+      uint32_t w;
+      if (votes) w = proto ? proto : b ? COA_DAG_INVALID_SIGNATURE : COA_DAG_OK;
+      else w = (b & 1) ? COA_DAG_INVALID_HEADER_ID : proto ? proto : (b & 2) ? COA_DAG_INVALID_SIGNATURE : COA_DAG_OK;
+      if (w != expect_words[k]) atomic_fetch_add(&wrong, 1);
+    }
+    *host_check_s = (now_us() - t1) * 1e-6;
+  }
+  *elapsed_s = (now_us() - t0) * 1e-6;
+  free(got);
+  if (atomic_load(&answered) != (long)n) atomic_fetch_add(&wrong, 1);
+  return atomic_load(&wrong);
+}
+
+/* ------------------------------------------------------------------------
+ * A certificate round through an existing queue from `producers` threads
+ * (tools/queue_verdict_ab.py): certificate k goes from thread k % producers.
+ *   route 0  verdict requests (coa_queue_submit_certificate_verdict): the
+ *            COA_DAG_* word comes back with the window
+ *   route 1  crypto requests (coa_queue_submit_certificate), then ONE host
+ *            thread of coa_cpu_certificate_verdict_from_status over the
+ *            COA_CERT_* bytes they answered (its time in *host_check_s, inside
+ *            *elapsed_s)
+ * Every word of either route is compared with expect_words.  Returns the
+ * number of wrong, failed or missing answers. */
+typedef struct {
+  coa_queue* q;
+  int route, p, producers;
+  size_t n;
+  const uint8_t *hdata, *ids, *origins, *hsigs, *vpks, *vsigs;
+  const uint64_t *hoff, *rounds_of, *voff;
+  const uint32_t *pcounts, *expect;
+  uint8_t* got;
+  atomic_int* wrong;
+  atomic_long* answered;
+} CertVerdictJob;
+
+static void* cert_verdict_thread(void* arg) {
+  CertVerdictJob* j = (CertVerdictJob*)arg;
+  for (size_t k = (size_t)j->p; k < j->n; k += (size_t)j->producers) {
+    VerdictReq* m = (VerdictReq*)malloc(sizeof(VerdictReq));
+    m->expect_word = j->expect + k;
+    m->got = j->route ? j->got + k : NULL;
+    m->wrong = j->wrong;
+    m->answered = j->answered;
+    const uint8_t* hdr = j->hdata + j->hoff[k];
+    const size_t hlen = (size_t)(j->hoff[k + 1] - j->hoff[k]);
+    const uint64_t v0 = j->voff[k], nv = j->voff[k + 1] - v0;
+    int rc;
+    if (j->route)
+      rc = coa_queue_submit_certificate(j->q, hdr, hlen, j->ids + 32 * k, j->origins + 32 * k, j->hsigs + 64 * k,
+                                        j->rounds_of[k], j->vpks + 32 * v0, j->vsigs + 64 * v0, nv, verdict_cb, m);
+    else
+      rc = coa_queue_submit_certificate_verdict(j->q, hdr, hlen, j->ids + 32 * k, j->origins + 32 * k,
+                                                j->hsigs + 64 * k, j->rounds_of[k], j->vpks + 32 * v0,
+                                                j->vsigs + 64 * v0, nv, j->pcounts[k], verdict_cb, m);
+    if (rc != COA_OK) {
+      atomic_fetch_add(j->wrong, 1);
+      atomic_fetch_add(j->answered, 1);
+      free(m);
+    }
+  }
+  return NULL;
+}
+
+int latc_queue_verdict_certificates(coa_queue* q, int route, int producers, const uint8_t* hdata, const uint64_t* hoff,
+                                    const uint8_t* ids, const uint8_t* origins, const uint8_t* hsigs,
+                                    const uint64_t* rounds_of, const uint8_t* vpks, const uint8_t* vsigs,
+                                    const uint64_t* voff, const uint32_t* pcounts, size_t n,
+                                    const uint32_t* expect_words, const uint8_t* committee_pks, const uint32_t* stakes,
+                                    const uint32_t* worker_ids, const uint64_t* worker_offsets, size_t n_authorities,
+                                    double* elapsed_s, double* host_check_s) {
+  if (!q || producers < 1 || producers > 64) return -1;
+  atomic_int wrong = 0;
+  atomic_long answered = 0;
+  uint8_t* got = (uint8_t*)malloc(n + 1);
+  uint32_t* words = (uint32_t*)malloc((n + 1) * sizeof(uint32_t));
+  if (!got || !words) return -1;
+  memset(got, 0xff, n + 1);
+  CertVerdictJob jobs[64];
+  pthread_t th[64];
+  const double t0 = now_us();
+  for (int p = 0; p < producers; p++) {
+    CertVerdictJob j = {q,     route,     p,    producers, n,       hdata,        ids, origins, hsigs,  vpks,
+                        vsigs, hoff,      rounds_of, voff, pcounts, expect_words, got, &wrong,  &answered};
+    jobs[p] = j;
+  }
+  for (int p = 0; p < producers; p++) pthread_create(&th[p], NULL, cert_verdict_thread, &jobs[p]);
+  for (int p = 0; p < producers; p++) pthread_join(th[p], NULL);
+  coa_queue_flush(q);
+  *host_check_s = 0;
+  if (route) {
+    const double t1 = now_us();
+    const int rc = coa_cpu_certificate_verdict_from_status(hdata, hoff, ids, origins, rounds_of, vpks, voff, n, pcounts,
+                                                           got, committee_pks, stakes, worker_ids, worker_offsets,
+                                                           n_authorities, words, 1);
+    if (rc != COA_OK) atomic_fetch_add(&wrong, 1);
+    for (size_t k = 0; k < n; k++)
+      if (words[k] != expect_words[k]) atomic_fetch_add(&wrong, 1);
+    *host_check_s = (now_us() - t1) * 1e-6;
+  }
+  *elapsed_s = (now_us() - t0) * 1e-6;
+  free(got);
+  free(words);
+  if (atomic_load(&answered) != (long)n) atomic_fetch_add(&wrong, 1);
+  return atomic_load(&wrong);
+}

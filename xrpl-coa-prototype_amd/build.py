@@ -24,7 +24,7 @@ SOURCES = ["coa_kernels.hip", "coa_halved.hip", "coa_batch.hip", "coa_committee.
 HEADERS = ["coa_fe.h", "coa_sc.h", "coa_ge.h", "coa_sha512.h", "coa_smul.h", "coa_kernels.h", "coa_batch.h", "coa_halved.h",
            "coa_committee.h", "coa_msm.h", "coa_fe_wave.h", "coa_ge_rows.h", "coa_halve.h", "coa_keycache.h",
            "coa_latency.h", "coa_queue.h", "coa_rcmp.h", "coa_lehmer.h", "coa_ge_sums.h", "coa_protocol.h",
-           "coa_protocol_dev.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
+           "coa_protocol_dev.h", "coa_prot_scan.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
            "coa_hostpool.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h"]
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffunction-sections", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 

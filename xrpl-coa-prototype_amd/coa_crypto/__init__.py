@@ -191,6 +191,13 @@ def lib():
         "coa_queue_submit_header": ([vp, P8, sz, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
         "coa_queue_submit_vote": ([vp, P8, ctypes.c_uint64, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
         "coa_queue_message_stats": ([vp, P64, P64, P64, P64], ctypes.c_int),
+        "coa_queue_submit_certificate_verdict": ([vp, P8, sz, P8, P8, P8, ctypes.c_uint64, P8, P8, sz,
+                                                  ctypes.c_uint32, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_submit_certificate_verdict_borrowed": ([vp, P8, sz, P8, P8, P8, ctypes.c_uint64, P8, P8, sz,
+                                                           ctypes.c_uint32, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_submit_header_verdict": ([vp, P8, sz, P8, P8, P8, ctypes.c_uint32, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_submit_vote_verdict": ([vp, P8, ctypes.c_uint64, P8, P8, P8, VERDICT_CB, vp], ctypes.c_int),
+        "coa_queue_verdict_stats": ([vp, P64, P64, P64, P64], ctypes.c_int),
         "coa_queue_digest_count": ([vp, P64], ctypes.c_int),
         "coa_queue_flush": ([vp], ctypes.c_int),
         "coa_queue_set_idle_launch": ([vp, ctypes.c_uint32], ctypes.c_int),
@@ -988,6 +995,27 @@ def message_lat_verify_device(device, headers, votes, status, stream=None):
     _check(f(device, ctypes.byref(a), status.data_ptr(), _handle(device, stream)))
 
 
+def message_lat_verdict_device(device, headers, pcounts, votes, words, stream=None):
+    """message_lat_verify_device answering whole verdicts (k_msg_verdict_lat,
+    the engine's internal coa_msg_lat_verdict_device): pcounts is the headers'
+    uint32 payload-count tensor (None without headers), words the uint32 tensor
+    [nh + nv] of COA_DAG_* words out.  Raises EngineError(COA_EINVAL) when the
+    committee was registered without stakes."""
+    f = lib().coa_msg_lat_verdict_device
+    f.argtypes = [ctypes.c_int, ctypes.POINTER(_MsgLatIn), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    f.restype = ctypes.c_int
+    a = _MsgLatIn()
+    if headers is not None:
+        a.hdr_data, a.hdr_off, a.hids, a.hauthors, a.hsigs = [t.data_ptr() for t in headers]
+        a.nh = headers[2].shape[0]
+    if votes is not None:
+        a.vids, a.vrounds, a.vorigins, a.vauthors, a.vsigs = [t.data_ptr() for t in votes]
+        a.nv = votes[0].shape[0]
+    rc = f(device, ctypes.byref(a), pcounts.data_ptr() if pcounts is not None else None, words.data_ptr(),
+           _handle(device, stream))
+    _check(-1 if rc == 1 else rc)  # no protocol table: COA_EINVAL
+
+
 # ------------------------------------------------------------- wire (f4)
 MSG_HEADER, MSG_VOTE, MSG_CERTIFICATE, MSG_CERT_REQUEST = 0, 1, 2, 3
 WIRE_ETRUNC, WIRE_EFORMAT, WIRE_EKEY = -10, -11, -12
@@ -1070,7 +1098,8 @@ class AggregationQueue:
     worker batch digests from any thread, get a concurrent.futures.Future per
     request -- True (Ok) / False (Err) for signatures, whole votes and vote
     batches, the CERT_BAD_* bits for certificates and whole headers, the
-    32-byte Digest for digests; the
+    32-byte Digest for digests, the COA_DAG_* verdict word (an int) for the
+    *_verdict requests; the
     engine error status raises EngineError in the future."""
 
     def __init__(self, max_batch=65536, max_delay_us=500):
@@ -1095,6 +1124,8 @@ class AggregationQueue:
             fut.set_result(Digest(bytes(verdicts[:32])))
         elif kind == "certificate":
             fut.set_result(int(verdicts[0]))
+        elif kind == "word":
+            fut.set_result(int.from_bytes(bytes(verdicts[:4]), "little"))
         else:
             fut.set_result(verdicts[0] == 0)
 
@@ -1116,7 +1147,19 @@ class AggregationQueue:
         """Future of the certificate's CERT_BAD_* bits (0 = all crypto Ok).
         borrow=True submits through coa_queue_submit_certificate_borrowed: the
         arrays built here are kept alive until the callback (no intake copy)."""
-        key, fut = self._register("certificate")
+        return self._submit_certificate(header_input, id_, origin, header_sig, round_, votes, borrow, None)
+
+    def submit_certificate_verdict(self, header_input, id_, origin, header_sig, round_, votes, payload_count,
+                                   borrow=False):
+        """Future of Certificate::verify's whole verdict, the COA_DAG_* word of
+        coa_certificate_verdict_many (never DAG_VOTES_OPEN), decided against
+        the committee of register_authorities; EngineError (COA_EINVAL) when
+        the window's committee generation has no protocol table."""
+        return self._submit_certificate(header_input, id_, origin, header_sig, round_, votes, borrow,
+                                        int(payload_count))
+
+    def _submit_certificate(self, header_input, id_, origin, header_sig, round_, votes, borrow, payload_count):
+        key, fut = self._register("certificate" if payload_count is None else "word")
         votes = list(votes)
         h = np.frombuffer(bytes(header_input), np.uint8).copy() if len(header_input) else np.zeros(1, np.uint8)
         i = np.frombuffer(bytes(id_), np.uint8).copy()
@@ -1128,9 +1171,15 @@ class AggregationQueue:
         if borrow:
             with self._lock:
                 self._borrowed[key] = (h, i, o, sg, pks, sgs)
-        submit = lib().coa_queue_submit_certificate_borrowed if borrow else lib().coa_queue_submit_certificate
+        if payload_count is None:
+            submit = lib().coa_queue_submit_certificate_borrowed if borrow else lib().coa_queue_submit_certificate
+            tail = (self._cb, key)
+        else:
+            submit = (lib().coa_queue_submit_certificate_verdict_borrowed if borrow
+                      else lib().coa_queue_submit_certificate_verdict)
+            tail = (payload_count, self._cb, key)
         rc = submit(self._q, _u8p(h), len(header_input), _u8p(i), _u8p(o), _u8p(sg), round_, _u8p(pks), _u8p(sgs),
-                    len(votes), self._cb, key)
+                    len(votes), *tail)
         if rc < 0:
             with self._lock:
                 self._borrowed.pop(key, None)
@@ -1140,27 +1189,48 @@ class AggregationQueue:
     def submit_header(self, header_input, id_, author, signature):
         """Future of Header::verify's crypto bits for one header: CERT_BAD_HEADER_ID
         | CERT_BAD_HEADER_SIG (0 = both Ok), coa_header_verify_many's semantics."""
-        key, fut = self._register("certificate")
+        return self._submit_header(header_input, id_, author, signature, None)
+
+    def submit_header_verdict(self, header_input, id_, author, signature, payload_count):
+        """Future of Header::verify's whole verdict, the COA_DAG_* word of
+        coa_header_verdict_many (see submit_certificate_verdict)."""
+        return self._submit_header(header_input, id_, author, signature, int(payload_count))
+
+    def _submit_header(self, header_input, id_, author, signature, payload_count):
+        key, fut = self._register("certificate" if payload_count is None else "word")
         h = np.frombuffer(bytes(header_input), np.uint8).copy() if len(header_input) else np.zeros(1, np.uint8)
         i = np.frombuffer(bytes(id_), np.uint8).copy()
         a = np.frombuffer(bytes(author), np.uint8).copy()
         sg = np.frombuffer(signature.flatten() if isinstance(signature, Signature) else bytes(signature),
                            np.uint8).copy()
-        rc = lib().coa_queue_submit_header(self._q, _u8p(h), len(header_input), _u8p(i), _u8p(a), _u8p(sg), self._cb,
-                                           key)
+        if payload_count is None:
+            rc = lib().coa_queue_submit_header(self._q, _u8p(h), len(header_input), _u8p(i), _u8p(a), _u8p(sg),
+                                               self._cb, key)
+        else:
+            rc = lib().coa_queue_submit_header_verdict(self._q, _u8p(h), len(header_input), _u8p(i), _u8p(a),
+                                                       _u8p(sg), payload_count, self._cb, key)
         self._submitted(key, rc)
         return fut
 
     def submit_vote(self, id_, round_, origin, author, signature):
         """Future of Vote::verify's signature check, True (Ok) / False (Err);
         Vote::digest is hashed by the engine (coa_vote_verify_many's semantics)."""
-        key, fut = self._register()
+        return self._submit_vote(id_, round_, origin, author, signature, False)
+
+    def submit_vote_verdict(self, id_, round_, origin, author, signature):
+        """Future of Vote::verify's whole verdict, the COA_DAG_* word of
+        coa_vote_verdict_many (see submit_certificate_verdict)."""
+        return self._submit_vote(id_, round_, origin, author, signature, True)
+
+    def _submit_vote(self, id_, round_, origin, author, signature, verdict):
+        key, fut = self._register("word" if verdict else "verdict")
         i = np.frombuffer(bytes(id_), np.uint8).copy()
         o = np.frombuffer(bytes(origin), np.uint8).copy()
         a = np.frombuffer(bytes(author), np.uint8).copy()
         sg = np.frombuffer(signature.flatten() if isinstance(signature, Signature) else bytes(signature),
                            np.uint8).copy()
-        rc = lib().coa_queue_submit_vote(self._q, _u8p(i), int(round_), _u8p(o), _u8p(a), _u8p(sg), self._cb, key)
+        submit = lib().coa_queue_submit_vote_verdict if verdict else lib().coa_queue_submit_vote
+        rc = submit(self._q, _u8p(i), int(round_), _u8p(o), _u8p(a), _u8p(sg), self._cb, key)
         self._submitted(key, rc)
         return fut
 
@@ -1170,6 +1240,13 @@ class AggregationQueue:
         v = [ctypes.c_uint64() for _ in range(4)]
         _check(lib().coa_queue_message_stats(self._q, *[ctypes.byref(x) for x in v]))
         return dict(zip(("headers", "votes", "latency_windows", "throughput_windows"), (x.value for x in v)))
+
+    def verdict_stats(self):
+        """coa_queue_verdict_stats: verdict requests answered by kind, and the
+        windows that held one."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        _check(lib().coa_queue_verdict_stats(self._q, *[ctypes.byref(x) for x in v]))
+        return dict(zip(("certificates", "headers", "votes", "verdict_windows"), (x.value for x in v)))
 
     def submit_digest(self, data):
         """Future of Digest(Sha512(data)[..32]) (worker/src/processor.rs:38)."""

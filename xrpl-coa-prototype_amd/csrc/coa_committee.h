@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "coa_protocol_dev.h"
 #include "coa_stage.h"
 
 // per-key comb of -A: 32 byte positions x 128 multiples x 24 dwords (384 KiB)
@@ -226,6 +227,21 @@ struct MsgLatArgs {
 };
 hipError_t coa_launch_msg_verify_lat(MsgLatArgs a, hipStream_t s);
 
+// The same window answered with whole Header::verify / Vote::verify verdicts
+// (k_msg_verdict_lat, the aggregation queue's all-verdict message windows):
+// each signature job also decides its message's protocol code -- the author's
+// stake and, for a header, its hpcounts[i] payload entries' worker ids -- from
+// the protocol table t of the same key-cache generation (t.keys == keys), and
+// the words written are coa_verdict_merge's (COA_DAG_*), not status bits:
+// published as (tag << 8) | word, or, without host_res, stored into status[]
+// (zero at launch; bit 31 of a header's word is in use until its second block
+// ends).
+struct MsgVerdictLatArgs : MsgLatArgs {
+  ProtTab t;
+  const uint32_t* hpcounts;  // [nh]
+};
+hipError_t coa_launch_msg_verdict_lat(MsgVerdictLatArgs a, hipStream_t s);
+
 // Device-resident entries of k_msg_verify_lat (the aggregation queue's
 // message windows, coa_queue_hip.cpp; not part of the public header).  The
 // arrays are device pointers laid out as coa_header_verify_many_device /
@@ -247,6 +263,14 @@ extern "C" int coa_msg_lat_verify_device(int device, const CoaMsgLatIn* in, uint
 // d_ctr[0..64] (65 device words, zero before the first call).
 extern "C" int coa_msg_lat_verify_publish(int device, const CoaMsgLatIn* in, uint32_t* d_ctr, uint32_t* host_res,
                                           uint32_t tag, void* stream);
+// The two entries above through k_msg_verdict_lat: h_pcounts [nh] are the
+// headers' payload counts (device), and the words are COA_DAG_* verdicts.
+// Return 1, with nothing enqueued, when the generation read has no protocol
+// table (a plain coa_committee_register).
+extern "C" int coa_msg_lat_verdict_device(int device, const CoaMsgLatIn* in, const uint32_t* h_pcounts,
+                                          uint32_t* d_words, void* stream);
+extern "C" int coa_msg_lat_verdict_publish(int device, const CoaMsgLatIn* in, const uint32_t* h_pcounts,
+                                           uint32_t* d_ctr, uint32_t* host_res, uint32_t tag, void* stream);
 
 // The exact decision of the messages the message kernels left open (raw words
 // with COA_CST_UNCACHED; the others pass through): verify_strict over the id

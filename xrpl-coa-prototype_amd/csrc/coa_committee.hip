@@ -51,18 +51,23 @@
 //                      workgroup per header digest: its lanes expand every
 //                      block's message schedule into LDS, then one wave
 //                      runs the rounds (coa_sha512.h, compress_kw).
+// k_msg_verify_lat is the latency body over a window's headers and votes, and
+// k_msg_verdict_lat the same answering their whole verdicts (wave 0 also
+// decides the protocol code of its message, coa_prot_scan.h).
 // kernels here exceed the +-128 KiB reach of an out-of-line fold (coa_fe.h)
 #define COA_RARE_INLINE
 #include "coa_committee.h"
 
 #include <cstddef>
 #include <cstdlib>
+#include <type_traits>
 
 #include "coa_fe.h"
 #include "coa_ge.h"
 #include "coa_halved.h"
 #include "coa_sc.h"
 #include "coa_keycache.h"
+#include "coa_prot_scan.h"
 #include "coa_rcmp.h"
 #include "coa_sha512.h"
 #include "coa_smul.h"
@@ -649,8 +654,35 @@ COA_DEV LatJob lat_job(const MsgLatArgs& a, uint32_t job) {
   return j;
 }
 
+// k_msg_verdict_lat (A: MsgVerdictLatArgs) answers verdict words instead: a
+// signature block's bits carry its message's protocol code in bits 8-15, and
+// the word that leaves is coa_verdict_merge(status bits, code).  Publishing,
+// the last block merges as it stores.  In status mode the block of a word that
+// ends last stores the merged word over it: a vote's only block at once, a
+// header's two blocks (digest and signature) told apart by bit 31, which each
+// sets with its OR -- the one that finds it set is the second.
+template <class A>
+constexpr bool kLatVerdict = std::is_same_v<A, MsgVerdictLatArgs>;
+constexpr uint32_t kLatFirstDone = 1u << 31;
+
 template <class A>
 COA_DEV void lat_block_done(const A& a, uint32_t c, uint32_t bits) {
+  if constexpr (kLatVerdict<A>) {
+    if (!a.host_res) {
+      if (c >= a.nh) {
+        a.status[c] = coa_verdict_merge(bits & 0xffu, (bits >> 8) & 0xffu);
+        return;
+      }
+      const uint32_t old =
+          __hip_atomic_fetch_or(a.status + c, bits | kLatFirstDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old & kLatFirstDone) {
+        const uint32_t st = old | bits;
+        __hip_atomic_store(a.status + c, coa_verdict_merge(st & 0xffu, (st >> 8) & 0xffu), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return;
+    }
+  }
   if (bits) (void)__hip_atomic_fetch_or(a.status + c, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (!a.host_res) return;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -660,7 +692,11 @@ COA_DEV void lat_block_done(const A& a, uint32_t c, uint32_t bits) {
   __hip_atomic_store(a.done_ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (uint32_t k = 0; k < lat_words(a); k++) {
     const uint32_t st = __hip_atomic_exchange(a.status + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.host_res + k, (a.tag << 8) | (st & 0xffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if constexpr (kLatVerdict<A>)
+      __hip_atomic_store(a.host_res + k, (a.tag << 8) | coa_verdict_merge(st & 0xffu, (st >> 8) & 0xffu),
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else
+      __hip_atomic_store(a.host_res + k, (a.tag << 8) | (st & 0xffu), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -750,6 +786,7 @@ COA_DEV void cert_lat_body(const A& a) {
       } else {
         bits = (eq && tfree) ? 0u : COA_CST_VOTES_INCONCLUSIVE;
       }
+      if constexpr (kLatVerdict<A>) bits |= pre & 0xff00u;  // the protocol code wave 0 handed over
     }
     LAT_MARK(1, 5)
     if (job == 0 && lane == 0) { HDR_MARK(5) }
@@ -773,8 +810,25 @@ COA_DEV void cert_lat_body(const A& a) {
     slot = key_lookup_u(a.keys, a.nk, pk);
     if (slot < 0) {
       bits = COA_CST_UNCACHED;
+      // outside the committee: the verdict needs no crypto (travels with skip)
+      if constexpr (kLatVerdict<A>) bits |= (uint32_t)COA_DAG_UNKNOWN_AUTHOR << 8;
       slot = 0;
     } else {
+      // the message's protocol code, beside wave 1's chain: the stake of the
+      // slot just found and a header's worker ids over the lanes
+      uint32_t code = 0;
+      if constexpr (kLatVerdict<A>) {
+        const uint8_t* hp = nullptr;
+        uint64_t hlen = 0;
+        uint32_t pc = 0;
+        if (job < a.nh) {  // a header's job (hdr is J.strict: set for votes too)
+          const uint64_t o0 = uni64(a.hdr_off[job]);
+          hlen = uni64(a.hdr_off[job + 1]) - o0;
+          hp = a.hdr_data + o0;
+          pc = coa_sha::uni(a.hpcounts[job]);
+        }
+        code = coa_prot::msg_code_wave(a.t, (uint32_t)slot, hp, hlen, pc, lane);
+      }
       uint64_t st[8];
       uint32_t h[16];
       if (J.digest) {  // Certificate::digest / Vote::digest on the scalar unit
@@ -806,6 +860,7 @@ COA_DEV void cert_lat_body(const A& a) {
       const bool a_ok = (kf & COA_KEY_DECOMPRESSES) != 0;
       pre = (s_ok ? 0u : 1u) | (a_ok ? 0u : 2u) | ((kf & COA_KEY_SMALL_ORDER) ? 4u : 0u) |
             ((kf & COA_KEY_TORSION_FREE) ? 0u : 8u);
+      if constexpr (kLatVerdict<A>) pre |= code << 8;  // bits 16-23 of the compare's prefix bits
 #pragma unroll
       for (int i = 0; i < 8; i++) dg[i] = k.v[i];
       tab = a.ktabs + (uint64_t)slot * COA_KEY_TAB_DWORDS;
@@ -853,6 +908,10 @@ __global__ void __launch_bounds__(192) k_cert_verify_lat(CertArgs a) { cert_lat_
 // job strict.  A header's signature job signs ids[i] as given, so it runs
 // beside that header's digest block, not after it.
 __global__ void __launch_bounds__(192) k_msg_verify_lat(MsgLatArgs a) { cert_lat_body(a); }
+
+// The same answering whole Header::verify / Vote::verify verdicts
+// (MsgVerdictLatArgs): no further launch, no lookup on the publishing tail.
+__global__ void __launch_bounds__(192) k_msg_verdict_lat(MsgVerdictLatArgs a) { cert_lat_body(a); }
 
 // The same with the certificate's arrays read from the kernel arguments.  The
 // buffer is addressed through the kernarg segment pointer (ci is the only
@@ -1191,6 +1250,13 @@ hipError_t coa_launch_msg_verify_lat(MsgLatArgs a, hipStream_t s) {
   if (a.nh + a.nv == 0) return hipSuccess;
   a.total_blocks = 2 * a.nh + a.nv;
   hipLaunchKernelGGL(k_msg_verify_lat, dim3(a.total_blocks), dim3(192), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t coa_launch_msg_verdict_lat(MsgVerdictLatArgs a, hipStream_t s) {
+  if (a.nh + a.nv == 0) return hipSuccess;
+  a.total_blocks = 2 * a.nh + a.nv;
+  hipLaunchKernelGGL(k_msg_verdict_lat, dim3(a.total_blocks), dim3(192), 0, s, a);
   return hipGetLastError();
 }
 

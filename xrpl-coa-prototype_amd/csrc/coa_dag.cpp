@@ -870,22 +870,25 @@ int coa_message_resolve_raw(const uint8_t* ids, const uint64_t* rounds, const ui
 }
 
 // k_msg_verify_lat over device arrays, on the pinned (the queue) or current
-// key-cache generation.
+// key-cache generation; with `verdict`, k_msg_verdict_lat against that
+// generation's protocol table and the headers' payload counts (returns 1,
+// nothing enqueued, when it has none).
 static int msg_lat_launch(int device, const CoaMsgLatIn* in, uint32_t* d_status, uint32_t* d_ctr, uint32_t* host_res,
-                          uint32_t tag, void* stream) {
+                          uint32_t tag, void* stream, bool verdict = false, const uint32_t* h_pcounts = nullptr) {
   const int rc = ensure_init();
   if (rc != COA_OK) return rc;
   if (!in) return fail(COA_EINVAL, "null argument");
   const size_t n = in->nh + in->nv;
   if (n == 0) return COA_OK;
   if ((in->nh && (!in->hdr_data || !in->hdr_off || !in->hids || !in->hauthors || !in->hsigs)) ||
-      (in->nv && (!in->vids || !in->vrounds || !in->vorigins || !in->vauthors || !in->vsigs)) || !d_status)
+      (in->nv && (!in->vids || !in->vrounds || !in->vorigins || !in->vauthors || !in->vsigs)) || !d_status ||
+      (verdict && in->nh && !h_pcounts))
     return fail(COA_EINVAL, "null argument");
   if (check_n(2 * n) != COA_OK) return COA_EINVAL;  // 2 nh + nv blocks
   Dev* d;
   hipStream_t s;
   if (const int e = enter_device(device, stream, d, s)) return e;
-  MsgLatArgs a{};
+  MsgVerdictLatArgs a{};
   a.hdr_data = in->hdr_data;
   a.hdr_off = in->hdr_off;
   a.ids = reinterpret_cast<const uint32_t*>(in->hids);
@@ -899,7 +902,8 @@ static int msg_lat_launch(int device, const CoaMsgLatIn* in, uint32_t* d_status,
   a.nh = (uint32_t)in->nh;
   a.nv = (uint32_t)in->nv;
   const KeySetP ks = keys_now(*d);  // see coa_lat_verify_device
-  key_args(a, *d, *ks);
+  if (verdict && !ks->has_prot) return 1;
+  key_args(static_cast<MsgLatArgs&>(a), *d, *ks);
   a.status = d_status;
   if (host_res) {
     a.host_res = host_res;
@@ -908,7 +912,13 @@ static int msg_lat_launch(int device, const CoaMsgLatIn* in, uint32_t* d_status,
   } else {
     HIP_TRY(hipMemsetAsync(d_status, 0, n * 4, s));
   }
-  HIP_TRY(coa_launch_msg_verify_lat(a, s));
+  if (verdict) {
+    (void)prot_tab(true, *ks, a.t);
+    a.hpcounts = h_pcounts;
+    HIP_TRY(coa_launch_msg_verdict_lat(a, s));
+  } else {
+    HIP_TRY(coa_launch_msg_verify_lat(a, s));
+  }
   return trail_keys(*d, ks, s);
 }
 
@@ -921,6 +931,64 @@ int coa_msg_lat_verify_publish(int device, const CoaMsgLatIn* in, uint32_t* d_ct
   if (!in || !d_ctr || !host_res || tag == 0) return fail(COA_EINVAL, "null argument or zero tag");
   if (in->nh + in->nv > 64) return fail(COA_EINVAL, "more messages than the result words hold");
   return msg_lat_launch(device, in, d_ctr + 1, d_ctr, host_res, tag, stream);
+}
+
+int coa_msg_lat_verdict_device(int device, const CoaMsgLatIn* in, const uint32_t* h_pcounts, uint32_t* d_words,
+                               void* stream) {
+  return msg_lat_launch(device, in, d_words, nullptr, nullptr, 0, stream, true, h_pcounts);
+}
+
+int coa_msg_lat_verdict_publish(int device, const CoaMsgLatIn* in, const uint32_t* h_pcounts, uint32_t* d_ctr,
+                                uint32_t* host_res, uint32_t tag, void* stream) {
+  if (!in || !d_ctr || !host_res || tag == 0) return fail(COA_EINVAL, "null argument or zero tag");
+  if (in->nh + in->nv > 64) return fail(COA_EINVAL, "more messages than the result words hold");
+  return msg_lat_launch(device, in, d_ctr + 1, d_ctr, host_res, tag, stream, true, h_pcounts);
+}
+
+int coa_window_verdict_device(int device, const CoaWindowVerdictIn* in, void* stream) {
+  const int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  if (!in) return fail(COA_EINVAL, "null argument");
+  const size_t n = in->nc + in->nh + in->nv;
+  if (n == 0) return COA_OK;
+  if ((in->nc && (!in->c_hdr_data || !in->c_hdr_off || !in->c_ids || !in->c_origins || !in->c_rounds || !in->c_voff ||
+                  !in->c_pcounts || !in->cert_raw || (in->n_votes && !in->c_vpks))) ||
+      (in->nh && (!in->h_hdr_data || !in->h_hdr_off || !in->h_pcounts || !in->h_authors)) ||
+      (in->nv && !in->v_authors) || ((in->nh || in->nv) && !in->msg_raw) || !in->words)
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n) != COA_OK || check_n(in->n_votes) != COA_OK) return COA_EINVAL;
+  Dev* d;
+  hipStream_t s;
+  if (const int e = enter_device(device, stream, d, s)) return e;
+  const KeySetP ks = keys_now(*d);  // pinned (the queue) or current
+  if (!ks->has_prot) return 1;      // the window's verdict requests get COA_EINVAL; nothing to run
+  ProtTab t;
+  (void)prot_tab(true, *ks, t);
+  WindowVerdictArgs a{};
+  a.cert.hdr_data = in->c_hdr_data;
+  a.cert.hdr_off = in->c_hdr_off;
+  a.cert.ids = reinterpret_cast<const uint32_t*>(in->c_ids);
+  a.cert.origins = reinterpret_cast<const uint32_t*>(in->c_origins);
+  a.cert.rounds = in->c_rounds;
+  a.cert.vpks = reinterpret_cast<const uint32_t*>(in->c_vpks);
+  a.cert.voff = in->c_voff;
+  a.cert.pcounts = in->c_pcounts;
+  a.cert.nc = (uint32_t)in->nc;
+  a.cert.nv = (uint32_t)in->n_votes;
+  if (in->nh) {
+    a.hdr.hdr_data = in->h_hdr_data;
+    a.hdr.hdr_off = in->h_hdr_off;
+    a.hdr.pcounts = in->h_pcounts;
+    a.hdr.authors = reinterpret_cast<const uint32_t*>(in->h_authors);
+    a.hdr.n = (uint32_t)in->nh;
+  }
+  a.vote.authors = reinterpret_cast<const uint32_t*>(in->v_authors);
+  a.vote.n = (uint32_t)in->nv;
+  a.cert_raw = in->cert_raw;
+  a.msg_raw = in->msg_raw;
+  a.words = in->words;
+  HIP_TRY(coa_launch_window_verdict(a, t, s));
+  return trail_keys(*d, ks, s);
 }
 
 size_t coa_message_workspace_bytes(size_t n) { return coa_msg_scratch_bytes(n); }

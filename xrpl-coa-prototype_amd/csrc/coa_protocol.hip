@@ -10,18 +10,23 @@
 //                     its votes
 //   k_msg_protocol    one header or vote per lane
 //   k_verdict_merge   one item per lane
+//   k_window_verdict  a queue window's certificates, headers and votes in one
+//                     launch: the two bodies above, each followed by the merge
 //
 // The kernels read the same arrays as k_cert_verify / k_msg_verify and are
 // independent of them; only the merge needs both answers.
 #include "coa_protocol_dev.h"
 
 #include "coa_keycache.h"
+#include "coa_prot_scan.h"
 #include "coa_protocol.h"
 
 namespace {
 
 using coa_kc::key_lookup;
 using coa_kc::load8;
+using coa_prot::has_worker;
+using coa_prot::worker_id_at;
 
 constexpr int kWaves = 4;  // certificates per 256-thread block
 
@@ -41,38 +46,15 @@ COA_DEV uint64_t wave_sum(uint64_t v) {
   return v;
 }
 
-// worker id k of a header: the u32 LE at byte 40 + 36 k + 32 of its digest
-// input (author | round | (digest | worker id)* | parents*), any alignment
-COA_DEV uint32_t worker_id_at(const uint8_t* hdr, uint32_t k) {
-  const uint8_t* p = hdr + 40 + 36 * (uint64_t)k + 32;
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-// committee.worker(author, id) (config/src/lib.rs:201-212) over the author's
-// sorted ids [lo, hi)
-COA_DEV bool has_worker(const uint32_t* __restrict__ wids, uint32_t lo, uint32_t hi, uint32_t id) {
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    const uint32_t w = wids[mid];
-    if (w == id) return true;
-    if (w < id) lo = mid + 1;
-    else hi = mid;
-  }
-  return false;
-}
-
 // One certificate per wavefront.  Reuse (messages.rs:202) is found through
 // first[slot], the lowest vote index that named committee slot `slot`, kept
 // in the wave's own slice of LDS: the strides run in vote order, every lane of
 // a stride enters its index with atomicMin before any lane reads, so vote j is
 // a reuse iff first[slot] < j.  A key outside the committee has no slot and
-// fails the stake test at its first occurrence, so slots suffice.
-__global__ void __launch_bounds__(64 * kWaves) k_cert_protocol(const CertProtArgs a, const ProtTab t) {
-  __shared__ uint32_t first_all[kWaves][COA_MAX_AUTHORITIES];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t c = blockIdx.x * kWaves + wave;
-  if (c >= a.nc) return;  // whole waves leave; no block-wide barrier below
-  uint32_t* first = first_all[wave];
+// fails the stake test at its first occurrence, so slots suffice.  Called by
+// a whole wavefront with its slice `first` of LDS; every lane returns the
+// certificate's protocol word.
+COA_DEV uint32_t cert_proto_word(const CertProtArgs& a, const ProtTab& t, uint32_t c, uint32_t lane, uint32_t* first) {
   const uint32_t nk = min(t.nk, (uint32_t)COA_MAX_AUTHORITIES);
   for (uint32_t s = lane; s < nk; s += 64) first[s] = 0xffffffffu;
 
@@ -129,22 +111,27 @@ __global__ void __launch_bounds__(64 * kWaves) k_cert_protocol(const CertProtArg
   }
   fail = wave_min(fail);
   weight = wave_sum(weight);
-  if (lane == 0) {
-    uint32_t w = 0;
-    if (genesis) w = COA_PROTO_GENESIS;                           // :190-193
-    else if (astake == 0) w = COA_DAG_UNKNOWN_AUTHOR;             // :53-54
-    else if (malformed) w = COA_DAG_MALFORMED_HEADER;             // :57-61
-    else if (fail != 0xffffffffu) w = fail;                       // :202-204
-    else if (weight < t.quorum) w = COA_DAG_REQUIRES_QUORUM;      // :208-211
-    a.proto[c] = w;
-  }
+  uint32_t w = 0;
+  if (genesis) w = COA_PROTO_GENESIS;                           // :190-193
+  else if (astake == 0) w = COA_DAG_UNKNOWN_AUTHOR;             // :53-54
+  else if (malformed) w = COA_DAG_MALFORMED_HEADER;             // :57-61
+  else if (fail != 0xffffffffu) w = fail;                       // :202-204
+  else if (weight < t.quorum) w = COA_DAG_REQUIRES_QUORUM;      // :208-211
+  return w;
+}
+
+__global__ void __launch_bounds__(64 * kWaves) k_cert_protocol(const CertProtArgs a, const ProtTab t) {
+  __shared__ uint32_t first_all[kWaves][COA_MAX_AUTHORITIES];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t c = blockIdx.x * kWaves + wave;
+  if (c >= a.nc) return;  // whole waves leave; no block-wide barrier below
+  const uint32_t w = cert_proto_word(a, t, c, lane, first_all[wave]);
+  if (lane == 0) a.proto[c] = w;
 }
 
 // One header (hdr_data set) or vote per lane: the author's stake (:53-54,
 // :133-136) and, for headers, the worker ids (:57-61).
-__global__ void __launch_bounds__(256) k_msg_protocol(const MsgProtArgs a, const ProtTab t) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
+COA_DEV uint32_t msg_proto_word(const MsgProtArgs& a, const ProtTab& t, uint32_t i) {
   uint32_t author[8];
   load8(author, a.authors + (uint64_t)i * 8);
   const int slot = key_lookup(t.keys, t.nk, author);
@@ -162,7 +149,13 @@ __global__ void __launch_bounds__(256) k_msg_protocol(const MsgProtArgs a, const
         if (!has_worker(t.wids, wlo, whi, worker_id_at(a.hdr_data + h0, k))) w = COA_DAG_MALFORMED_HEADER;
     }
   }
-  a.proto[i] = w;
+  return w;
+}
+
+__global__ void __launch_bounds__(256) k_msg_protocol(const MsgProtArgs a, const ProtTab t) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  a.proto[i] = msg_proto_word(a, t, i);
 }
 
 __global__ void __launch_bounds__(256) k_verdict_merge(const uint32_t* __restrict__ raw,
@@ -170,6 +163,33 @@ __global__ void __launch_bounds__(256) k_verdict_merge(const uint32_t* __restric
                                                        uint32_t* __restrict__ verdicts, uint32_t n) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) verdicts[i] = coa_verdict_merge(raw[i], proto[i]);
+}
+
+// The whole verdict of an aggregation-queue window in one launch, over the
+// window's staged arrays and the raw status words its crypto launches wrote
+// earlier on the stream.  The leading cert_blocks blocks take one certificate
+// per wavefront (cert_proto_word); the blocks after them one header or vote
+// per lane (msg_proto_word), the headers first.  Each item's protocol word is
+// merged with its raw word at once: word c of a.words belongs to certificate
+// c, word nc + i to header i, word nc + nh + j to vote j.
+// The message-role blocks carry the certificate role's 16 KB of LDS unused:
+// a CU runs at most 32 waves, eight such blocks, whose 128 KB fit its 160 KB,
+// so the table does not bound their occupancy.
+__global__ void __launch_bounds__(64 * kWaves) k_window_verdict(const WindowVerdictArgs a, const ProtTab t) {
+  __shared__ uint32_t first_all[kWaves][COA_MAX_AUTHORITIES];
+  if (blockIdx.x < a.cert_blocks) {
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.x * kWaves + wave;
+    if (c >= a.cert.nc) return;  // whole waves leave; no block-wide barrier below
+    const uint32_t w = cert_proto_word(a.cert, t, c, lane, first_all[wave]);
+    if (lane == 0) a.words[c] = coa_verdict_merge(a.cert_raw[c], w);
+    return;
+  }
+  const uint32_t i = (blockIdx.x - a.cert_blocks) * blockDim.x + threadIdx.x;
+  const uint32_t nh = a.hdr.n, nv = a.vote.n;
+  if (i >= nh + nv) return;
+  const uint32_t w = i < nh ? msg_proto_word(a.hdr, t, i) : msg_proto_word(a.vote, t, i - nh);
+  a.words[a.cert.nc + i] = coa_verdict_merge(a.msg_raw[i], w);
 }
 
 }  // namespace
@@ -190,5 +210,14 @@ hipError_t coa_launch_verdict_merge(const uint32_t* raw, const uint32_t* proto, 
                                     hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_verdict_merge, dim3((n + 255) / 256), dim3(256), 0, s, raw, proto, verdicts, n);
+  return hipGetLastError();
+}
+
+hipError_t coa_launch_window_verdict(WindowVerdictArgs a, const ProtTab& t, hipStream_t s) {
+  const uint32_t msgs = a.hdr.n + a.vote.n;
+  a.cert_blocks = (a.cert.nc + kWaves - 1) / kWaves;
+  const uint32_t blocks = a.cert_blocks + (msgs + 64 * kWaves - 1) / (64 * kWaves);
+  if (blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_window_verdict, dim3(blocks), dim3(64 * kWaves), 0, s, a, t);
   return hipGetLastError();
 }

@@ -70,6 +70,9 @@ struct LaneMetrics {
   uint64_t windows = 0, max_window = 0, max_in_flight = 0;  // booked at the launch
   uint64_t sig = 0, batch = 0, cert = 0, dig = 0, hdr = 0, vote = 0;
   uint64_t msg_lat = 0, msg_tp = 0;  // message windows by the backend's route
+  // verdict requests by kind (each also counted in cert / hdr / vote) and the
+  // windows that held one (coa_queue_verdict_stats)
+  uint64_t v_cert = 0, v_hdr = 0, v_vote = 0, v_windows = 0;
   uint64_t retried = 0, recovered = 0, failed = 0;
   // the slowest window (launch call -> outputs in host memory) and the
   // longest wait for a free slot
@@ -91,6 +94,10 @@ struct LaneMetrics {
     vote += L.nvt;
     if (L.msg_route == Launch::MSG_LATENCY) msg_lat++;
     if (L.msg_route == Launch::MSG_THROUGHPUT) msg_tp++;
+    v_cert += L.n_vc;
+    v_hdr += L.n_vh;
+    v_vote += L.n_vvt;
+    if (L.verdicts()) v_windows++;
     batch += L.ng;
     cert += L.nc;
     dig += L.nd;

@@ -18,15 +18,20 @@ struct WindowPack {
   // signatures: 128-byte records msg | pk | R | s (the latency kernel), or
   // msgs | pks | sigs
   Sec v_recs, v_msgs, v_pks, v_sigs;
-  CertPack cert;   // the nine certificate arrays (hdata with 16 bytes of slack)
+  // the nine certificate arrays (hdata with 16 bytes of slack); pcounts, the
+  // certificates' u32 payload counts, only in a window with verdict requests
+  CertPack cert;
   Sec d_data, d_off;  // digest inputs (16 bytes of slack) and their nd + 1 offsets
-  MsgPack hdr;     // ids, authors, sigs, hoff, hdata (slack as above); empty without headers
+  MsgPack hdr;     // ids, authors, sigs, hoff, hdata (slack as above), pcounts as cert's; empty without headers
   MsgPack vote;    // ids, rounds, origins, authors, sigs
   size_t in_total = 0;
   Sec o_sigs;   // nv verdict bytes, or nv words for the latency kernel
   Sec o_certs;  // nc raw status words
   Sec o_digs;   // nd x 64
   Sec o_msgs;   // the headers' raw status words, then the votes'
+  // verdict words (k_window_verdict) of the certificates, then the headers,
+  // then the votes: only in a window with verdict requests
+  Sec o_words;
   size_t out_total = 0;
 };
 
@@ -40,9 +45,11 @@ inline WindowPack window_layout(const Launch& L, bool sig_lat) {
   p.cert.ids = c.take(L.nc * 32), p.cert.origins = c.take(L.nc * 32), p.cert.hsigs = c.take(L.nc * 64);
   p.cert.rounds = c.take(L.nc * 8);
   p.cert.vpks = c.take(L.nvotes * 32), p.cert.vsigs = c.take(L.nvotes * 64), p.cert.voff = c.take((L.nc + 1) * 8);
+  p.cert.pcounts = c.take(L.verdicts() ? L.nc * 4 : 0);
   p.d_data = c.take(L.dbytes + 16), p.d_off = c.take((L.nd + 1) * 8);
   p.hdr.hdata = c.take(L.nhd ? L.hdbytes + 16 : 0), p.hdr.hoff = c.take(L.nhd ? (L.nhd + 1) * 8 : 0);
   p.hdr.ids = c.take(L.nhd * 32), p.hdr.authors = c.take(L.nhd * 32), p.hdr.sigs = c.take(L.nhd * 64);
+  p.hdr.pcounts = c.take(L.verdicts() ? L.nhd * 4 : 0);
   p.vote.ids = c.take(L.nvt * 32), p.vote.rounds = c.take(L.nvt * 8), p.vote.origins = c.take(L.nvt * 32);
   p.vote.authors = c.take(L.nvt * 32), p.vote.sigs = c.take(L.nvt * 64);
   p.in_total = c.end;
@@ -51,6 +58,7 @@ inline WindowPack window_layout(const Launch& L, bool sig_lat) {
   p.o_certs = o.take(L.nc * 4);
   p.o_digs = o.take(L.nd * 64);
   p.o_msgs = o.take((L.nhd + L.nvt) * 4);
+  p.o_words = o.take(L.verdicts() ? (L.nc + L.nhd + L.nvt) * 4 : 0);
   p.out_total = o.end;
   return p;
 }
@@ -69,7 +77,17 @@ inline void window_pack(uint8_t* h, const WindowPack& p, const Launch& L, std::v
   cho[0] = cvo[0] = dof[0] = 0;
   if (L.nhd) hdo[0] = 0;
   size_t v = 0, c = 0, cv = 0, hb = 0, dn = 0, db = 0, mh = 0, mhb = 0, mt = 0;
+  // payload counts: zero for every crypto request, a verdict request's own
+  // (a part's vectors reach as far as its last verdict request)
+  auto counts = [h](const Sec& s, size_t at, const std::vector<uint32_t>& pc, size_t n) {
+    if (!s.bytes) return;
+    uint32_t* to = reinterpret_cast<uint32_t*>(h + s.at) + at;
+    std::memset(to, 0, n * 4);
+    if (!pc.empty()) std::memcpy(to, pc.data(), std::min(pc.size(), n) * 4);
+  };
   for (const Window* w : L.parts) {
+    counts(p.cert.pcounts, c, w->c_pcounts, w->nc);
+    counts(p.hdr.pcounts, mh, w->hd_pcounts, w->nhd);
     if (p.v_recs.bytes) {
       for (size_t i = 0; i < w->nv; i++) {
         uint8_t* r = h + p.v_recs.at + (v + i) * 128;
@@ -135,15 +153,28 @@ enum Route { ROUTE_STAGED, ROUTE_SIG_INLINE, ROUTE_CERT_PUBLISH, ROUTE_MSG_PUBLI
 // Raw message status words (a published word's tag ignored) -> the
 // headers' COA_CERT_BAD_HEADER_* bits and the votes' verdicts; a message by an
 // author outside the committee is left open for the resolver, a header's
-// digest bit kept.
-inline void scatter_messages(Window& w, const uint32_t* hst, const uint32_t* vst) {
+// digest bit kept.  A verdict request is never left open: its word of `hw` /
+// `vw` (the window's verdict words; null when none were computed, the words
+// then stay "failed") answers it.  hw == hst / vw == vst: the status words are
+// k_msg_verdict_lat's verdict words themselves, message codes in 8 bits under
+// a published word's tag.
+inline void scatter_messages(Window& w, const uint32_t* hst, const uint32_t* vst, const uint32_t* hw = nullptr,
+                             const uint32_t* vw = nullptr) {
   w.m_defer.clear();
   for (size_t i = 0; i < w.nhd; i++) {
+    if (w.verdict_header(i)) {
+      if (hw) w.hd_words[i] = hw == hst ? hw[i] & 0xffu : hw[i];
+      continue;
+    }
     const bool open = (hst[i] & COA_CST_UNCACHED) != 0;
     if (open) w.m_defer.push_back((uint32_t)i);
     w.hd_out[i] = (uint8_t)(hst[i] & (open ? 1u : 3u));
   }
   for (size_t i = 0; i < w.nvt; i++) {
+    if (w.verdict_vote(i)) {
+      if (vw) w.vt_words[i] = vw == vst ? vw[i] & 0xffu : vw[i];
+      continue;
+    }
     if (vst[i] & COA_CST_UNCACHED) w.m_defer.push_back((uint32_t)(w.nhd + i));
     w.vt_out[i] = (vst[i] & COA_CST_BAD_HEADER_SIG) ? 1 : 0;
   }
@@ -151,11 +182,18 @@ inline void scatter_messages(Window& w, const uint32_t* hst, const uint32_t* vst
 
 // Raw certificate status words -> COA_CERT_* bits; the certificates the
 // fused kernel could not decide alone keep their raw words and are left
-// open for the resolver.
-inline void scatter_certs(Window& w, const uint32_t* st) {
+// open for the resolver.  A verdict request gets its word of `cw` (as in
+// scatter_messages) and is left open only when that is COA_DAG_VOTES_OPEN:
+// every earlier check passed and the votes need the exact check.
+inline void scatter_certs(Window& w, const uint32_t* st, const uint32_t* cw = nullptr) {
   w.c_raw.assign(st, st + w.nc);
   w.c_defer.clear();
   for (size_t c = 0; c < w.nc; c++) {
+    if (w.verdict_cert(c)) {
+      if (cw) w.c_words[c] = cw[c];
+      if (cw && cw[c] == COA_DAG_VOTES_OPEN) w.c_defer.push_back((uint32_t)c);
+      continue;
+    }
     // exactly the words coa_certificate_resolve_raw re-decides: a key
     // outside the committee, or inconclusive votes not already bad
     const bool open = (st[c] & COA_CST_UNCACHED) ||
@@ -176,10 +214,21 @@ inline void window_scatter(const Launch& L, const WindowPack& p, const uint8_t* 
   const uint32_t* sst = words(p.o_sigs, ROUTE_SIG_INLINE);
   const uint32_t* cst = words(p.o_certs, ROUTE_CERT_PUBLISH);
   const uint32_t* mst = words(p.o_msgs, ROUTE_MSG_PUBLISH);
+  // the verdict words, when the window has the section and the kernel ran
+  const uint32_t* vw = p.o_words.bytes && L.verdict_rc == COA_OK && route == ROUTE_STAGED && !L.msg_words
+                           ? reinterpret_cast<const uint32_t*>(out + p.o_words.at)
+                           : nullptr;
+  auto at = [vw](size_t i) { return vw ? vw + i : nullptr; };
+  // ... or, from k_msg_verdict_lat, the messages' own words (a published
+  // word's tag is taken off as the word is read)
+  const bool mw = L.msg_words && L.verdict_rc == COA_OK;
   const bool sig_lat = p.v_recs.bytes != 0;
   size_t v = 0, c = 0, dn = 0, mh = 0, mt = 0;
   for (Window* w : L.parts) {
-    scatter_messages(*w, mst + mh, mst + L.nhd + mt);
+    if (mw)
+      scatter_messages(*w, mst + mh, mst + L.nhd + mt, mst + mh, mst + L.nhd + mt);
+    else
+      scatter_messages(*w, mst + mh, mst + L.nhd + mt, at(L.nc + mh), at(L.nc + L.nhd + mt));
     if (w->nv && sig_lat) {
       for (size_t i = 0; i < w->nv; i++) w->v_out[i] = (uint8_t)(sst[v + i] & 0xffu);
     } else if (w->nv) {
@@ -191,7 +240,7 @@ inline void window_scatter(const Launch& L, const WindowPack& p, const uint8_t* 
       for (size_t i = 0; i < w->nc; i++) st[i] = cst[c + i] & 0xffu;  // the tag off
       scatter_certs(*w, st);
     } else if (w->nc) {
-      scatter_certs(*w, cst + c);
+      scatter_certs(*w, cst + c, at(c));
     }
     w->g_defer = w->ng > 0;
     v += w->nv;
@@ -259,7 +308,8 @@ inline Deferred gather_deferred(const std::vector<Window*>& ws) {
 
 // The answers back to the items gather_deferred took, in its order: the
 // messages' re-decided raw words (d.m_raw), the certificates' COA_CERT_* bytes
-// and the bare batches' verdicts.
+// and the bare batches' verdicts.  An open verdict certificate passed every
+// earlier check (COA_DAG_VOTES_OPEN), so its exact answer is the vote bit.
 inline void put_messages(const std::vector<Window*>& ws, const Deferred& d) {
   size_t j[2] = {0, 0};
   for (Window* w : ws)
@@ -274,7 +324,10 @@ inline void put_messages(const std::vector<Window*>& ws, const Deferred& d) {
 }
 inline void put_certs(const std::vector<Window*>& ws, const uint8_t* status) {
   for (Window* w : ws)
-    for (uint32_t c : w->c_defer) w->c_out[c] = *status++;
+    for (uint32_t c : w->c_defer) {
+      if (w->verdict_cert(c)) w->c_words[c] = (*status & COA_CERT_BAD_VOTES) ? COA_DAG_INVALID_VOTES : COA_DAG_OK;
+      w->c_out[c] = *status++;
+    }
 }
 inline void put_groups(const std::vector<Window*>& ws, const uint8_t* verdicts) {
   for (Window* w : ws)

@@ -46,6 +46,16 @@
 // The backend (coa_queue.h) is the HIP one (coa_queue_hip.cpp) or, in the
 // sanitizer and CPU tests, a stub.
 //
+// Verdict requests (coa_queue_submit_*_verdict): a certificate, header or
+// vote whose callback gets the reference's whole DagResult as one COA_DAG_*
+// word (n = 4) instead of crypto bits.  They are items of the same arrays as
+// the crypto requests of their kind, marked in the window (Window::c_vreq,
+// hd_vreq, vt_vreq, with the payload counts), so they share shards, windows,
+// slots, retries and ordering; the backend decides their words in the window
+// and leaves open only certificates whose votes need the exact check.  A
+// window whose key-cache generation has no protocol table answers them with
+// COA_EINVAL (Launch::verdict_rc) and the failed word -- no engine failure.
+//
 // Metrics (coa_queue_metrics): per-kind request counts, window sizes,
 // windows in flight, pending depth, retried / recovered / failed windows, the
 // submit -> callback wait time of every request (mean, max, p50/p99 from a
@@ -81,7 +91,9 @@ using coa_q::Launch;
 using coa_q::WaitTally;
 using coa_q::Window;
 
-enum Kind : uint8_t { K_VERIFY, K_BATCH, K_CERT, K_DIGEST, K_HEADER, K_VOTE };
+// The *_V kinds are the verdict requests: items of the same arrays as K_CERT,
+// K_HEADER and K_VOTE (idx counts both), answered with a COA_DAG_* word.
+enum Kind : uint8_t { K_VERIFY, K_BATCH, K_CERT, K_DIGEST, K_HEADER, K_VOTE, K_CERT_V, K_HEADER_V, K_VOTE_V };
 
 inline void cpu_relax() {
 #if defined(__x86_64__)
@@ -110,19 +122,31 @@ struct Req {
 // open in its window (Window::c_defer, m_defer, g_defer): the resolver's.
 inline bool is_deferred(const Req& r, const Window& w) {
   switch (r.kind) {
-    case K_CERT: return w.is_deferred_cert(r.idx);
+    case K_CERT:
+    case K_CERT_V: return w.is_deferred_cert(r.idx);
     case K_BATCH: return w.g_defer;
     case K_HEADER: return w.is_deferred_msg(r.idx);
     case K_VOTE: return w.is_deferred_msg((uint32_t)w.nhd + r.idx);
     case K_VERIFY:
-    case K_DIGEST: break;
+    case K_DIGEST:
+    case K_HEADER_V:  // answered by the protocol word alone, in their window
+    case K_VOTE_V: break;
   }
   return false;
 }
+// A verdict request's callback: one COA_DAG_* word (n = 4), with the window's
+// status or, when that is fine, the verdict requests' own (COA_EINVAL: no
+// protocol table).  The word is the failed one whenever the status is negative.
+inline void answer_word(const Req& r, const std::vector<uint32_t>& words, int rc, int verdict_rc) {
+  r.cb(r.user, rc != COA_OK ? rc : verdict_rc, reinterpret_cast<const uint8_t*>(words.data() + r.idx), 4);
+}
 // The request's callback with the launch's (or the resolver pass's) status
 // and its output in the window.
-inline void answer_req(const Req& r, const Window& w, int rc) {
+inline void answer_req(const Req& r, const Window& w, int rc, int verdict_rc) {
   switch (r.kind) {
+    case K_CERT_V: answer_word(r, w.c_words, rc, verdict_rc); break;
+    case K_HEADER_V: answer_word(r, w.hd_words, rc, verdict_rc); break;
+    case K_VOTE_V: answer_word(r, w.vt_words, rc, verdict_rc); break;
     case K_VERIFY: r.cb(r.user, rc, w.v_out.data() + r.idx, r.n); break;
     case K_BATCH: r.cb(r.user, rc, w.g_out.data() + r.idx, 1); break;
     case K_CERT: r.cb(r.user, rc, w.c_out.data() + r.idx, 1); break;
@@ -665,7 +689,7 @@ struct Lane {
         if (any_open && is_deferred(r, w)) continue;  // the resolver answers it
         if (((k - g.lo) & 31) == 31) tnow = now_ns();
         t.add((double)(tnow - r.t0) * 1e-3);
-        answer_req(r, w, rc);
+        answer_req(r, w, rc, f.L.verdict_rc);
       }
     };
     if (n_helpers > 0 && nreq >= kParallelAnswer && runs.size() > 1) {
@@ -729,7 +753,7 @@ struct Lane {
       for (const Part& d : jobs)
         for (const Req& r : d.reqs) {
           waits.add((double)(now_ns() - r.t0) * 1e-3);
-          answer_req(r, *d.w, rc);
+          answer_req(r, *d.w, rc, COA_OK);
         }
       const int64_t t2 = now_ns();
       for (Part& d : jobs) shards[d.shard].recycle(d.w, nullptr);
@@ -822,9 +846,25 @@ inline void put(std::vector<uint8_t>& v, const uint8_t* src) {
 // A certificate request: `r` holds the caller's pointers; a copy (r.owned)
 // appends their bytes to the window's own buffer, one append per
 // field, and keeps the offsets (bind() turns them into pointers at the take).
-inline int submit_cert(coa_queue* q, Window::CertRef r, coa_verdict_cb cb, void* user) {
+// `pcount`: a verdict request's payload count (null: a crypto request).
+inline bool count_fits(uint32_t payload_count, size_t header_len) {
+  return payload_count == 0 || 40 + 36 * (uint64_t)payload_count <= header_len;
+}
+// Item idx of a kind becomes a verdict request: its flag and, for the kinds
+// that have one, its payload count (the vectors reach as far as idx).
+inline void mark_verdict(std::vector<uint8_t>& vreq, std::vector<uint32_t>* pcounts, size_t idx, uint32_t pcount) {
+  vreq.resize(idx + 1, 0);
+  vreq[idx] = 1;
+  if (pcounts) {
+    pcounts->resize(idx + 1, 0);
+    (*pcounts)[idx] = pcount;
+  }
+}
+inline int submit_cert(coa_queue* q, Window::CertRef r, coa_verdict_cb cb, void* user,
+                       const uint32_t* pcount = nullptr) {
   if (!q || (r.hlen && !r.hdr) || !r.id || !r.origin || !r.hsig || (r.nv && (!r.vpks || !r.vsigs)) || !cb)
     return COA_EINVAL;
+  if (pcount && !count_fits(*pcount, r.hlen)) return COA_EINVAL;
   Intake in(q, K_CERT);
   if (!in.ok()) return COA_EINVAL;
   Window& w = in.w;
@@ -845,7 +885,51 @@ inline int submit_cert(coa_queue* q, Window::CertRef r, coa_verdict_cb cb, void*
   w.c_refs.push_back(r);
   w.c_votes += r.nv;
   w.c_hbytes += r.hlen;
-  in.done(K_CERT, (uint32_t)w.nc++, 1, 1 + r.nv, cb, user);
+  if (pcount) {
+    mark_verdict(w.c_vreq, &w.c_pcounts, w.nc, *pcount);
+    w.n_vc++;
+  }
+  in.done(pcount ? K_CERT_V : K_CERT, (uint32_t)w.nc++, 1, 1 + r.nv, cb, user);
+  return COA_OK;
+}
+
+inline int submit_header(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t* id,
+                         const uint8_t* author, const uint8_t* sig, coa_verdict_cb cb, void* user,
+                         const uint32_t* pcount = nullptr) {
+  if (!q || (header_len && !header_data) || !id || !author || !sig || !cb) return COA_EINVAL;
+  if (pcount && !count_fits(*pcount, header_len)) return COA_EINVAL;
+  Intake in(q, K_HEADER);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
+  if (header_len) w.hd_data.insert(w.hd_data.end(), header_data, header_data + header_len);
+  w.hd_offs.push_back(w.hd_data.size());
+  put<32>(w.hd_ids, id);
+  put<32>(w.hd_authors, author);
+  put<64>(w.hd_sigs, sig);
+  if (pcount) {
+    mark_verdict(w.hd_vreq, &w.hd_pcounts, w.nhd, *pcount);
+    w.n_vh++;
+  }
+  in.done(pcount ? K_HEADER_V : K_HEADER, (uint32_t)w.nhd++, 1, 1, cb, user);
+  return COA_OK;
+}
+
+inline int submit_vote(coa_queue* q, const uint8_t* id, uint64_t round, const uint8_t* origin, const uint8_t* author,
+                       const uint8_t* sig, coa_verdict_cb cb, void* user, bool verdict) {
+  if (!q || !id || !origin || !author || !sig || !cb) return COA_EINVAL;
+  Intake in(q, K_VOTE);
+  if (!in.ok()) return COA_EINVAL;
+  Window& w = in.w;
+  put<32>(w.vt_ids, id);
+  w.vt_rounds.push_back(round);
+  put<32>(w.vt_origins, origin);
+  put<32>(w.vt_authors, author);
+  put<64>(w.vt_sigs, sig);
+  if (verdict) {
+    mark_verdict(w.vt_vreq, nullptr, w.nvt, 0);
+    w.n_vvt++;
+  }
+  in.done(verdict ? K_VOTE_V : K_VOTE, (uint32_t)w.nvt++, 1, 1, cb, user);
   return COA_OK;
 }
 }  // namespace
@@ -976,31 +1060,53 @@ int coa_queue_submit_digest(coa_queue* q, const uint8_t* data, size_t len, coa_v
 
 int coa_queue_submit_header(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
                             const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
-  if (!q || (header_len && !header_data) || !id || !author || !sig || !cb) return COA_EINVAL;
-  Intake in(q, K_HEADER);
-  if (!in.ok()) return COA_EINVAL;
-  Window& w = in.w;
-  if (header_len) w.hd_data.insert(w.hd_data.end(), header_data, header_data + header_len);
-  w.hd_offs.push_back(w.hd_data.size());
-  put<32>(w.hd_ids, id);
-  put<32>(w.hd_authors, author);
-  put<64>(w.hd_sigs, sig);
-  in.done(K_HEADER, (uint32_t)w.nhd++, 1, 1, cb, user);
-  return COA_OK;
+  return submit_header(q, header_data, header_len, id, author, sig, cb, user);
 }
 
 int coa_queue_submit_vote(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
                           const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
-  if (!q || !id || !origin || !author || !sig || !cb) return COA_EINVAL;
-  Intake in(q, K_VOTE);
-  if (!in.ok()) return COA_EINVAL;
-  Window& w = in.w;
-  put<32>(w.vt_ids, id);
-  w.vt_rounds.push_back(round);
-  put<32>(w.vt_origins, origin);
-  put<32>(w.vt_authors, author);
-  put<64>(w.vt_sigs, sig);
-  in.done(K_VOTE, (uint32_t)w.nvt++, 1, 1, cb, user);
+  return submit_vote(q, id, round, origin, author, sig, cb, user, false);
+}
+
+// The verdict requests: the same intake with the item marked (and its payload
+// count kept); a count that overruns its header is refused here.
+int coa_queue_submit_certificate_verdict(coa_queue* q, const uint8_t* header_data, size_t header_len,
+                                         const uint8_t id[32], const uint8_t origin[32], const uint8_t header_sig[64],
+                                         uint64_t round, const uint8_t* vote_pks, const uint8_t* vote_sigs,
+                                         size_t n_votes, uint32_t payload_count, coa_verdict_cb cb, void* user) {
+  return submit_cert(q, {header_data, id, origin, header_sig, vote_pks, vote_sigs, header_len, round, n_votes, true},
+                     cb, user, &payload_count);
+}
+
+int coa_queue_submit_certificate_verdict_borrowed(coa_queue* q, const uint8_t* header_data, size_t header_len,
+                                                  const uint8_t id[32], const uint8_t origin[32],
+                                                  const uint8_t header_sig[64], uint64_t round,
+                                                  const uint8_t* vote_pks, const uint8_t* vote_sigs, size_t n_votes,
+                                                  uint32_t payload_count, coa_verdict_cb cb, void* user) {
+  return submit_cert(q, {header_data, id, origin, header_sig, vote_pks, vote_sigs, header_len, round, n_votes, false},
+                     cb, user, &payload_count);
+}
+
+int coa_queue_submit_header_verdict(coa_queue* q, const uint8_t* header_data, size_t header_len, const uint8_t id[32],
+                                    const uint8_t author[32], const uint8_t sig[64], uint32_t payload_count,
+                                    coa_verdict_cb cb, void* user) {
+  return submit_header(q, header_data, header_len, id, author, sig, cb, user, &payload_count);
+}
+
+int coa_queue_submit_vote_verdict(coa_queue* q, const uint8_t id[32], uint64_t round, const uint8_t origin[32],
+                                  const uint8_t author[32], const uint8_t sig[64], coa_verdict_cb cb, void* user) {
+  return submit_vote(q, id, round, origin, author, sig, cb, user, true);
+}
+
+int coa_queue_verdict_stats(coa_queue* q, uint64_t* certificates, uint64_t* headers, uint64_t* votes,
+                            uint64_t* verdict_windows) {
+  if (!q) return COA_EINVAL;
+  Lane& L = q->lanes[coa_q::LANE_VERIFY];
+  std::lock_guard<std::mutex> l(L.mu);
+  if (certificates) *certificates = L.m.v_cert;
+  if (headers) *headers = L.m.v_hdr;
+  if (votes) *votes = L.m.v_vote;
+  if (verdict_windows) *verdict_windows = L.m.v_windows;
   return COA_OK;
 }
 

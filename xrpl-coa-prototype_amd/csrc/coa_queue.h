@@ -20,6 +20,7 @@ namespace coa_q {
 constexpr uint8_t kVerdictErr = 1;  // signatures, bare vote batches, whole votes
 constexpr uint8_t kCertFailed = COA_CERT_BAD_HEADER_ID | COA_CERT_BAD_HEADER_SIG | COA_CERT_BAD_VOTES;
 constexpr uint8_t kHeaderFailed = COA_CERT_BAD_HEADER_ID | COA_CERT_BAD_HEADER_SIG;
+constexpr uint32_t kWordFailed = COA_DAG_INVALID_SIGNATURE;  // every verdict kind's word
 
 // One intake shard's requests, packed contiguously by kind (the arrays the
 // engine's batched entry points take).  A launch takes the windows of every
@@ -74,6 +75,21 @@ struct Window {
   // the resolver (ascending): header i as i, vote j as nhd + j.  An open
   // header's hd_out already holds its digest bit.
   std::vector<uint32_t> m_defer;
+  // Verdict requests (coa_queue_submit_*_verdict) are certificates, headers
+  // and votes of the arrays above, marked here: flag i set makes item i a
+  // verdict request, answered with its word of *_words (a COA_DAG_* verdict)
+  // instead of its byte of *_out.  The flag vectors and the payload counts
+  // reach only as far as the last verdict request of their kind (shorter than
+  // the kind's count, empty without one: a crypto request appends nothing and
+  // its payload count is 0).
+  size_t n_vc = 0, n_vh = 0, n_vvt = 0;  // verdict requests among nc, nhd, nvt
+  std::vector<uint8_t> c_vreq, hd_vreq, vt_vreq;
+  std::vector<uint32_t> c_pcounts, hd_pcounts;
+  std::vector<uint32_t> c_words, hd_words, vt_words;  // nc, nhd, nvt words; sized only with verdict requests
+  bool verdict_cert(size_t c) const { return c < c_vreq.size() && c_vreq[c]; }
+  bool verdict_header(size_t i) const { return i < hd_vreq.size() && hd_vreq[i]; }
+  bool verdict_vote(size_t i) const { return i < vt_vreq.size() && vt_vreq[i]; }
+  bool verdicts() const { return n_vc + n_vh + n_vvt != 0; }
   // Left open by Backend::complete (or retry) for the lane's resolver
   // (Backend::resolve): certificates the fused kernel could not decide alone
   // (their raw status words kept) and, with g_defer, every bare vote batch.
@@ -107,6 +123,9 @@ struct Window {
     d_out.assign(nd * 32, 0);
     hd_out.assign(nhd, kHeaderFailed);
     vt_out.assign(nvt, kVerdictErr);
+    c_words.assign(n_vc ? nc : 0, kWordFailed);
+    hd_words.assign(n_vh ? nhd : 0, kWordFailed);
+    vt_words.assign(n_vvt ? nvt : 0, kWordFailed);
     c_raw.clear();
     close_open();
   }
@@ -120,7 +139,10 @@ struct Window {
   // "Failed" outputs for exactly the requests left open (a resolver pass that
   // failed: whatever it wrote is overwritten, the other outputs stay).
   void fail_open() {
-    for (uint32_t c : c_defer) c_out[c] = kCertFailed;
+    for (uint32_t c : c_defer) {
+      c_out[c] = kCertFailed;
+      if (verdict_cert(c)) c_words[c] = kWordFailed;
+    }
     for (uint32_t m : m_defer) {
       if (m < nhd)
         hd_out[m] = kHeaderFailed;
@@ -160,6 +182,9 @@ struct Window {
   // under the intake lock).
   void reset() {
     nv = ng = nc = nd = nhd = nvt = 0;
+    n_vc = n_vh = n_vvt = 0;
+    for (auto* v : {&c_vreq, &hd_vreq, &vt_vreq}) v->clear();
+    for (auto* v : {&c_pcounts, &hd_pcounts, &c_words, &hd_words, &vt_words}) v->clear();
     intake_ns = 0;
     c_raw.clear();
     close_open();
@@ -192,6 +217,18 @@ struct Launch {
   // the route the backend gave the launch's messages (coa_queue_message_stats)
   enum { MSG_NONE = 0, MSG_LATENCY, MSG_THROUGHPUT };
   int msg_route = MSG_NONE;
+  // verdict requests among nc, nhd, nvt, and their status when the window's
+  // key-cache generation has no protocol table (COA_EINVAL, set by the
+  // backend: no engine failure -- the rest of the window is answered as usual)
+  size_t n_vc = 0, n_vh = 0, n_vvt = 0;
+  int verdict_rc = COA_OK;
+  bool verdicts() const { return n_vc + n_vh + n_vvt != 0; }
+  // every message of the window is a verdict request and no certificate is
+  // (the window k_msg_verdict_lat can answer alone, when it is small enough)
+  bool all_message_verdicts() const { return nhd + nvt != 0 && n_vh == nhd && n_vvt == nvt && n_vc == 0; }
+  // set by the backend: the messages' words (the o_msgs section, or the
+  // published words) are verdict words already, k_msg_verdict_lat's
+  bool msg_words = false;
   int rc = COA_OK;     // engine status (negative = failure), set by the backend
   int slot = -1;       // backend slot the launch ran on
   int attempts = 0;    // launches of this window (1 + retries)
@@ -212,6 +249,7 @@ struct Launch {
   }
   void tally() {
     nv = ng = nc = nd = nvotes = hbytes = dbytes = gvotes = nhd = nvt = hdbytes = 0;
+    n_vc = n_vh = n_vvt = 0;
     for (const Window* w : parts) {
       nv += w->nv;
       ng += w->ng;
@@ -224,12 +262,17 @@ struct Launch {
       nhd += w->nhd;
       nvt += w->nvt;
       hdbytes += w->hd_data.size();
+      n_vc += w->n_vc;
+      n_vh += w->n_vh;
+      n_vvt += w->n_vvt;
     }
   }
   size_t items() const { return nv + nd + nc + nvotes + gvotes + nhd + nvt; }
   void reset_outputs() {
     for (Window* w : parts) w->reset_outputs();
     rc = COA_OK;
+    verdict_rc = COA_OK;
+    msg_words = false;
     msg_route = MSG_NONE;
   }
 };

@@ -56,6 +56,26 @@
 //                 Messages by authors outside the registered committee
 //                 (COA_CST_UNCACHED) are left open (Window::m_defer) and
 //                 decided by resolve() with coa_message_resolve_raw
+//   verdicts      a window that holds a verdict request (coa_queue_submit_*_verdict)
+//                 takes the staged route; after the crypto entries of its
+//                 certificates, headers and votes, ONE k_window_verdict launch
+//                 (coa_window_verdict_device) decides the protocol checks of
+//                 all of them over the same staged arrays -- plus the two
+//                 payload-count sections -- and merges them with the raw status
+//                 words into the verdict-word section of the output block,
+//                 which the one D2H copy carries.  The scatter gives every
+//                 verdict request its word; only a certificate left
+//                 COA_DAG_VOTES_OPEN goes to resolve().  A pinned generation
+//                 without protocol table: Launch::verdict_rc = COA_EINVAL,
+//                 nothing launched for the verdicts, the rest as usual.
+//                 Except a window whose messages are all verdict requests,
+//                 at most COA_QUEUE_MSG_LAT_MAX of them, with no certificate
+//                 verdict (Launch::msg_words): k_msg_verdict_lat decides the
+//                 protocol code in each signature job and writes the merged
+//                 words where the crypto messages' status words go -- on
+//                 ROUTE_MSG_PUBLISH when alone and at most 64
+//                 (coa_msg_lat_verdict_publish), else staged
+//                 (coa_msg_lat_verdict_device) -- with no further launch
 //   digests       coa_sha512_many_device (worker/src/processor.rs:38)
 //   vote batches  coa_ed25519_verify_batch_groups in resolve() (host
 //                 pointers; bare batches are rare next to whole certificates)
@@ -83,6 +103,7 @@
 #include "coa_committee.h"
 #include "coa_env.h"
 #include "coa_latency.h"
+#include "coa_protocol_dev.h"
 #include "coa_qstage.h"
 #include "coa_queue.h"
 
@@ -578,7 +599,14 @@ class HipBackend : public coa_q::Backend {
       sl.route = coa_q::ROUTE_SIG_INLINE;
       return enqueue_sig_inline(sl, L, inject, clk);
     }
-    if (inline_ok_ && L.nc > 0 && L.nc <= COA_PUBLISH_WORDS && alone_c && lat_words(sl) != nullptr &&
+    // a window with a verdict request takes the staged route: its words are a
+    // section of the output block (a certificate's published word has 8 status
+    // bits, no room for a vote index).  Except message windows of verdict
+    // requests alone, small enough for the latency kernel: k_msg_verdict_lat
+    // answers their words itself, on the routes of the crypto messages
+    const bool verd = L.verdicts();
+    L.msg_words = msg_lat && L.all_message_verdicts();
+    if (inline_ok_ && !verd && L.nc > 0 && L.nc <= COA_PUBLISH_WORDS && alone_c && lat_words(sl) != nullptr &&
         ctr_words(sl) != nullptr) {
       sl.route = coa_q::ROUTE_CERT_PUBLISH;
       const int rc = enqueue_cert_publish(sl, L, inject, clk);
@@ -586,10 +614,16 @@ class HipBackend : public coa_q::Backend {
       sl.route = coa_q::ROUTE_STAGED;  // too many jobs for the latency kernel
     }
     if (msgs) L.msg_route = msg_lat ? coa_q::Launch::MSG_LATENCY : coa_q::Launch::MSG_THROUGHPUT;
-    if (inline_ok_ && msg_lat && msgs <= COA_PUBLISH_WORDS && alone_m && lat_words(sl) != nullptr &&
-        ctr_words(sl) != nullptr) {
+    if (inline_ok_ && (!verd || L.msg_words) && msg_lat && msgs <= COA_PUBLISH_WORDS && alone_m &&
+        lat_words(sl) != nullptr && ctr_words(sl) != nullptr) {
       sl.route = coa_q::ROUTE_MSG_PUBLISH;
-      return enqueue_msg_publish(sl, L, inject, clk);
+      const int rc = enqueue_msg_publish(sl, L, inject, clk);
+      if (rc != 1) return rc;
+      // no protocol table: no kernel ran and nothing is published; the input
+      // copy in flight is waited for as on the staged route
+      sl.route = coa_q::ROUTE_STAGED;
+      L.verdict_rc = COA_EINVAL;
+      return record(sl, clk);
     }
     return enqueue_staged(sl, L, msg_lat, inject, clk);
   }
@@ -650,6 +684,11 @@ class HipBackend : public coa_q::Backend {
     return in;
   }
 
+  // The headers' payload counts in block d (a window with verdict requests).
+  static const uint32_t* h_pcounts(const void* d, const coa_q::WindowPack& p) {
+    return reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(d) + p.hdr.pcounts.at);
+  }
+
   // A few signatures alone (Header::verify / Vote::verify at low load): the
   // packed records go in the kernel arguments and the verdict words come back
   // by the kernel's own stores, as coa_ed25519_verify_strict does -- the
@@ -704,10 +743,13 @@ class HipBackend : public coa_q::Backend {
     {
       KeyUse keys(sl);
       clk.mark(coa_q::Launch::ENQ_PIN);
-      rc = coa_msg_lat_verify_publish(sl.dev, &in, sl.dctr, sl.lres, sl.ltag, sl.s);
+      if (L.msg_words)
+        rc = coa_msg_lat_verdict_publish(sl.dev, &in, h_pcounts(sl.din, sl.pack), sl.dctr, sl.lres, sl.ltag, sl.s);
+      else
+        rc = coa_msg_lat_verify_publish(sl.dev, &in, sl.dctr, sl.lres, sl.ltag, sl.s);
     }
     clk.mark(coa_q::Launch::ENQ_LAUNCH);
-    return rc == COA_OK ? record(sl, clk) : rc;
+    return rc == COA_OK ? record(sl, clk) : rc;  // 1: see enqueue()
   }
 
   // Everything else: ONE H2D copy, the device-resident entry of each kind the
@@ -739,7 +781,14 @@ class HipBackend : public coa_q::Backend {
                                                       out_words(p.o_certs), sl.ws, sl.s, keysort_ ? 1 : 0);
       }
       uint32_t* d_mst = out_words(p.o_msgs);  // the headers' status words, then the votes'
-      if (rc == COA_OK && msg_lat) {
+      if (rc == COA_OK && L.msg_words) {  // the messages' verdict words, in the status words' place
+        const CoaMsgLatIn in = msg_lat_in(d, p, L);
+        rc = coa_msg_lat_verdict_device(sl.dev, &in, h_pcounts(d, p), d_mst, sl.s);
+        if (rc == 1) {  // no protocol table in the pinned generation: the verdict requests' own status
+          L.verdict_rc = COA_EINVAL;
+          rc = COA_OK;
+        }
+      } else if (rc == COA_OK && msg_lat) {
         const CoaMsgLatIn in = msg_lat_in(d, p, L);
         rc = coa_msg_lat_verify_device(sl.dev, &in, d_mst, sl.s);
       } else if (rc == COA_OK && msgs) {
@@ -750,6 +799,28 @@ class HipBackend : public coa_q::Backend {
         if (rc == COA_OK && L.nvt)
           rc = coa_vote_verify_many_device(sl.dev, v.ids, v.rounds, v.origins, v.authors, v.sigs, L.nvt,
                                            d_mst + L.nhd, sl.ws, sl.s);
+      }
+      // the verdict words of every certificate, header and vote of a window
+      // with verdict requests: one launch behind the crypto entries, over the
+      // same staged arrays and their raw words
+      if (rc == COA_OK && L.verdicts() && !L.msg_words) {
+        const CertIn c = cert_view(d, p.cert);
+        const MsgIn h = msg_view(d, p.hdr, false), v = msg_view(d, p.vote, true);
+        CoaWindowVerdictIn in{};
+        in.c_hdr_data = c.hdr_data, in.c_hdr_off = c.hdr_off, in.c_ids = c.ids, in.c_origins = c.origins;
+        in.c_rounds = c.rounds, in.c_vpks = c.vpks, in.c_voff = c.voff;
+        in.c_pcounts = reinterpret_cast<const uint32_t*>(d + p.cert.pcounts.at);
+        in.nc = L.nc, in.n_votes = L.nvotes;
+        in.h_hdr_data = h.hdr_data, in.h_hdr_off = h.hdr_off, in.h_authors = h.authors;
+        in.h_pcounts = reinterpret_cast<const uint32_t*>(d + p.hdr.pcounts.at);
+        in.nh = L.nhd;
+        in.v_authors = v.authors, in.nv = L.nvt;
+        in.cert_raw = out_words(p.o_certs), in.msg_raw = d_mst, in.words = out_words(p.o_words);
+        rc = coa_window_verdict_device(sl.dev, &in, sl.s);
+        if (rc == 1) {  // no protocol table in the pinned generation: the verdict requests' own status
+          L.verdict_rc = COA_EINVAL;
+          rc = COA_OK;
+        }
       }
       if (rc == COA_OK && L.nd)
         rc = coa_sha512_many_device(sl.dev, d + p.d_data.at, reinterpret_cast<const uint64_t*>(d + p.d_off.at), L.nd,
