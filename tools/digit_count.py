@@ -17,7 +17,12 @@ count and a SHA-256 of the hot-path instruction text (labels, comments and
 directives stripped, block labels renumbered per function), so two builds are
 compared by diffing two small files.
 
-usage: python tools/digit_count.py [--json FILE] [coa_halved.s]
+For both k_pre_halve<3, *> instances it also lists the hot-path loops with
+their body counts (the squaring runs of the (p-5)/8 chains are the loops
+without memory instructions).  -D NAME=VALUE is passed to the compiler
+(-D COA_PRE_POW29=0: the radix-2^32 decompression).
+
+usage: python tools/digit_count.py [--json FILE] [-D NAME=VALUE ...] [coa_halved.s]
        (without a .s argument the file is compiled here with build.py's flags)"""
 import argparse
 import collections
@@ -171,9 +176,10 @@ def fmt(c):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", metavar="FILE")
+    ap.add_argument("-D", dest="defines", action="append", default=[], metavar="NAME=VALUE")
     ap.add_argument("asm", nargs="?")
     a = ap.parse_args()
-    text = open(a.asm or compile_s("coa_halved.hip")).read()
+    text = open(a.asm or compile_s("coa_halved.hip", ["-D" + d for d in a.defines])).read()
     meta = metadata(text)
     report = {}
     for name, m in meta.items():
@@ -196,6 +202,11 @@ def main():
         if name.startswith(PRE):
             lines = function_lines(text, name + ":")
             print(f"{name[:name.index('Ev') + 2]} hot-path text:", fmt(tally(lines, 0, len(lines) - 1)))
+            bodies = [dict({k: tally(lines, lo, hi)[k] for k in KEYS}, memory=sum(1 for _, op, _ in lines[lo:hi + 1] if op and op.startswith(
+                ("global_", "scratch_", "buffer_", "flat_", "ds_", "s_load")))) for lo, hi in sorted(loops(lines))]
+            arith = [b for b in bodies if not b["memory"] and b["v_mad_u64_u32"] >= 40]
+            print("  arithmetic loop bodies (instructions, mads):", [(b["all"], b["v_mad_u64_u32"]) for b in arith])
+            report[name].update(arith_loops=arith)
     for name, m in meta.items():
         print(f"  {name[:44]:44s} vgpr {m['vgpr_count']:4d} spill {m['vgpr_spill_count']:3d} sgpr {m['sgpr_count']:3d}"
               f" private {m['private_segment_fixed_size']:4d} lds {m['group_segment_fixed_size']}")

@@ -25,7 +25,8 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "xrpl-coa-prototype_amd", "lib", "libcoa_verify.so")
+# the library the profiled run loaded: COA_VERIFY_LIB in an A/B session, else the in-tree build
+LIB = os.environ.get("COA_VERIFY_LIB") or os.path.join(ROOT, "xrpl-coa-prototype_amd", "lib", "libcoa_verify.so")
 
 
 def rows(root, sub):

@@ -25,7 +25,7 @@ HEADERS = ["coa_fe.h", "coa_sc.h", "coa_ge.h", "coa_sha512.h", "coa_smul.h", "co
            "coa_committee.h", "coa_msm.h", "coa_fe_wave.h", "coa_ge_rows.h", "coa_halve.h", "coa_keycache.h",
            "coa_latency.h", "coa_queue.h", "coa_rcmp.h", "coa_lehmer.h", "coa_ge_sums.h", "coa_protocol.h",
            "coa_protocol_dev.h", "coa_prot_scan.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
-           "coa_hostpool.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h"]
+           "coa_hostpool.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge_dec29.h"]
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffunction-sections", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 
 
@@ -76,11 +76,12 @@ def build(verbose=False):
 
 
 ARITH_HEADERS = ["coa_fe.h", "coa_fe_wave.h", "coa_sc.h", "coa_halve.h", "coa_lehmer.h", "coa_ge.h", "coa_smul.h",
-                 "coa_halved.h", "coa_ge_sums.h", "coa_ge_rows.h", "coa_sums_tail.h"]
-# test-only device libraries around the arithmetic headers: (source under tests/arith/, library under lib/)
-ARITH_LIBS = [("arith_check.hip", "libcoa_arithcheck.so"), ("alias_check.hip", "libcoa_aliascheck.so"),
-              ("sums_check.hip", "libcoa_sumscheck.so"), ("tail_check.hip", "libcoa_tailcheck.so")]
-ARITH_SRC = os.path.join(ROOT, "tests", "arith", ARITH_LIBS[0][0])
+                 "coa_halved.h", "coa_ge_sums.h", "coa_ge_rows.h", "coa_sums_tail.h", "coa_fe_pow29.h"]
+# test-only device libraries around the arithmetic headers: (sources under tests/arith/, library under lib/)
+ARITH_LIBS = [(["arith_check.hip", "pow29_check.hip"], "libcoa_arithcheck.so"),
+              (["alias_check.hip"], "libcoa_aliascheck.so"), (["sums_check.hip"], "libcoa_sumscheck.so"),
+              (["tail_check.hip"], "libcoa_tailcheck.so")]
+ARITH_SRC = os.path.join(ROOT, "tests", "arith", ARITH_LIBS[0][0][0])
 ARITH_LIB = os.path.join(LIBDIR, ARITH_LIBS[0][1])
 
 
@@ -91,13 +92,15 @@ def _build_arithcheck():
     is and with -DCOA_RARE_INLINE, so both assembled forms of the rare carry
     blocks of coa_fe.h are in its library (symbols *_out / *_inl)."""
     todo = []
-    for src_name, lib_name in ARITH_LIBS:
-        src, lib = os.path.join(ROOT, "tests", "arith", src_name), os.path.join(LIBDIR, lib_name)
-        if not os.path.exists(src):
+    for src_names, lib_name in ARITH_LIBS:
+        srcs = [os.path.join(ROOT, "tests", "arith", n) for n in src_names]
+        srcs = [s for s in srcs if os.path.exists(s)]
+        lib = os.path.join(LIBDIR, lib_name)
+        if not srcs:
             continue
-        deps = [src, os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ARITH_HEADERS]
+        deps = srcs + [os.path.abspath(__file__)] + [os.path.join(CSRC, h) for h in ARITH_HEADERS]
         if not (os.path.exists(lib) and os.path.getmtime(lib) >= _newest(deps)):
-            todo.append((src, lib))
+            todo.append((srcs, lib))
     if not todo:
         return
 
@@ -112,11 +115,12 @@ def _build_arithcheck():
             raise RuntimeError(f"hipcc failed for {os.path.basename(src)} ({variant}):\n{r.stderr[-6000:]}")
         return obj
 
-    jobs = [(src, v) for src, _ in todo for v in ("out", "inl")]
+    jobs = [(src, v) for srcs, _ in todo for src in srcs for v in ("out", "inl")]
     with concurrent.futures.ThreadPoolExecutor(max_workers=len(jobs)) as ex:
-        objs = list(ex.map(one, jobs))
-    for k, (src, lib) in enumerate(todo):
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + objs[2 * k:2 * k + 2]
+        objs = dict(zip(jobs, ex.map(one, jobs)))
+    for srcs, lib in todo:
+        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", lib] + \
+              [objs[(src, v)] for src in srcs for v in ("out", "inl")]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"{os.path.basename(lib)} link failed:\n{r.stderr[-6000:]}")

@@ -40,6 +40,15 @@
 
 #include "coa_fe.h"
 #include "coa_ge.h"
+// k_pre_halve's decompressions: 1 = coa_ge_dec29.h (the (p-5)/8 chain on
+// 29-bit limbs), 0 = ge_decompress / ge_is_small_order of coa_ge.h.  Compile
+// time only (tools/build_variant.py builds the other library for A/B runs).
+#ifndef COA_PRE_POW29
+#define COA_PRE_POW29 1
+#endif
+#if COA_PRE_POW29
+#include "coa_ge_dec29.h"
+#endif
 #include "coa_ge_sums.h"
 #include "coa_halve.h"
 #include "coa_halved_dev.h"
@@ -235,8 +244,14 @@ COA_DEV bool pre_one(const uint8_t* __restrict__ pks, const uint8_t* __restrict_
   load8_u4(sw, sigs + (uint64_t)i * 64 + 32);
   const bool s_ok = which || sc_is_canonical(sw);
   ge_p3 Q;
+#if COA_PRE_POW29
+  ge_dec29_squares sq;
+  const bool dec = ge_decompress_29(Q, sq, w);
+  const bool small = ge_is_small_order_29(Q, sq);
+#else
   const bool dec = ge_decompress(Q, w);
   const bool small = ge_is_small_order(Q);
+#endif
   const bool ok = s_ok && dec && !small;
   fe_neg(Q.X, Q.X);
   fe_neg(Q.T, Q.T);
