@@ -6,7 +6,8 @@
 //
 // build.py compiles this file twice into lib/libcoa_arithcheck.so: as is (the
 // rare carry blocks out of line, as in coa_kernels.hip / coa_halved.hip) and
-// with -DCOA_RARE_INLINE (as in coa_latency.hip / coa_committee.hip).  The
+// with -DCOA_RARE_INLINE (as in coa_latency.hip, coa_committee.hip, coa_cert_lat.hip
+// and coa_keybuild.hip).  The
 // two copies live in different namespaces and export coa_arith_run_out /
 // coa_arith_run_inl; coa_arith_run picks one.  Not part of the C ABI of
 // include/coa_verify.h.

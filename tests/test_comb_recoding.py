@@ -6,7 +6,7 @@
   POS 13; W 16, POS 16: k < l).
 * For the keys (k < l), the top radix-2^20 digit is at most 2^13, which is
   what lets k_key_wcomb20 leave the entries (12, m > 2^16) unbuilt.
-* coa_committee.hip k_key_wcomb20: entry (j, m) = m 2^(20 j) is the sum of the
+* coa_keybuild.hip k_key_wcomb20: entry (j, m) = m 2^(20 j) is the sum of the
   radix-256 comb entries (q, b0), (q+1, b1), (q+2, b2) with signed bytes
   |b_i| <= 128 (the radix-256 comb's range) and q + 2 <= 31 wherever a digit
   can reach it."""

@@ -4,8 +4,8 @@ output limbs (tests/arith/arith_check.hip wraps each primitive in a trivial
 kernel; tests/arith_ref.py has the references and builds the operands).
 
 Exact integer comparisons only.  Each op runs in both assembled forms of the
-rare carry blocks (out of line, and COA_RARE_INLINE as coa_latency.hip and
-coa_committee.hip build them), on operands constructed to take every path --
+rare carry blocks (out of line, and COA_RARE_INLINE as coa_latency.hip,
+coa_committee.hip, coa_cert_lat.hip and coa_keybuild.hip build them), on operands constructed to take every path --
 the second carry pass and its carry out, 0 / 1 final subtractions of l, a
 rippling row normalisation -- placed so that a wave holds only rare lanes, one
 rare lane (first, last), alternating ones and none; with a partial last wave

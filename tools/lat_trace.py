@@ -24,10 +24,10 @@ def build():
 
     b.build()
     os.makedirs(OUT, exist_ok=True)
-    obj = os.path.join(OUT, "coa_committee.o")
-    subprocess.run([b.HIPCC] + b.COMMON + ["-DCOA_LAT_TRACE", "-c", os.path.join(b.CSRC, "coa_committee.hip"), "-o", obj],
+    obj = os.path.join(OUT, "coa_cert_lat.o")
+    subprocess.run([b.HIPCC] + b.COMMON + ["-DCOA_LAT_TRACE", "-c", os.path.join(b.CSRC, "coa_cert_lat.hip"), "-o", obj],
                    check=True)
-    objs = [obj if s == "coa_committee.hip" else os.path.join(b.OBJDIR, s + ".o") for s in b.SOURCES]
+    objs = [obj if s == "coa_cert_lat.hip" else os.path.join(b.OBJDIR, s + ".o") for s in b.SOURCES]
     subprocess.run([b.HIPCC, f"--offload-arch={b.ARCH}", "-shared", "-fPIC", "-o", os.path.join(OUT, "libcoa_verify.so")]
                    + objs, check=True)
 

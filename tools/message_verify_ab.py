@@ -35,7 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "xrpl-coa-prototype_amd"))
 import numpy as np  # noqa: E402
 
 HEADER_BYTES = 3336
-KERNEL_SOURCE = os.path.join(ROOT, "xrpl-coa-prototype_amd", "csrc", "coa_committee.hip")
+KERNEL_SOURCE = os.path.join(ROOT, "xrpl-coa-prototype_amd", "csrc", "coa_committee.hip")  # k_msg_verify
 
 
 def _git_head():

@@ -41,7 +41,10 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
 
-from message_verify_ab import HEADER_BYTES, KERNEL_SOURCE, Inputs, _git_head, _stats  # noqa: E402
+from message_verify_ab import HEADER_BYTES, Inputs, _git_head, _stats  # noqa: E402
+
+# k_msg_verify_lat
+KERNEL_SOURCE = os.path.join(ROOT, "xrpl-coa-prototype_amd", "csrc", "coa_cert_lat.hip")
 
 SWEEP = (1, 16, 64, 128, 512, 2048, 8192)
 DRAIN = 65536

@@ -43,7 +43,8 @@ construction above.  Every shape is warmed first.
       crypto requests on that build and on this one, each in processes of its
       own (tools/queue_paced_crypto.py), the two builds alternated.
 
-    python tools/queue_verdict_ab.py [--reps 3] [--sweep-reps 20] [--parent-tree DIR] [--out FILE] [--git-head SHA]
+    python tools/queue_verdict_ab.py [--reps 3] [--sweep-reps 20] [--sweep-only] [--parent-tree DIR] [--out FILE]
+                                     [--git-head SHA]
 
 Writes the record as JSON to --out and prints each row.
 """
@@ -66,7 +67,7 @@ from queue_message_ab import DRAIN, _expected, _host, _spread  # noqa: E402
 
 PAYLOAD = 8
 SWEEP = (1, 64, 128, 512)
-SOURCES = ("coa_committee.hip", "coa_committee.h", "coa_prot_scan.h", "coa_protocol.hip", "coa_protocol.h",
+SOURCES = ("coa_cert_lat.hip", "coa_lat_job.h", "coa_job_bits.h", "coa_committee.h", "coa_prot_scan.h", "coa_protocol.hip", "coa_protocol.h",
            "coa_queue_hip.cpp", "coa_queue.cpp", "coa_qstage.h")
 OK, BAD_ID, UNKNOWN_AUTHOR, MALFORMED, BAD_SIG = 0, 1, 2, 3, 4
 
@@ -277,6 +278,7 @@ def main():
     ap.add_argument("--sweep-reps", type=int, default=20)
     ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: part (p)")
     ap.add_argument("--n", type=int, default=DRAIN)
+    ap.add_argument("--sweep-only", action="store_true", help="part (a) alone (an A/B of two libraries: COA_VERIFY_LIB)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "queue_verdict_ab.json"))
     ap.add_argument("--git-head", default=None, help="recorded as is (for a tree run without its .git)")
     args = ap.parse_args()
@@ -313,6 +315,12 @@ def main():
               "results": parent_rows}
     for n in SWEEP:
         record["results"] += _sweep(cc, torch, x, stream, hw, vw, min(n, args.n), args.sweep_reps)
+    if args.sweep_only:
+        cc.committee_register(np.zeros((0, 32), np.uint8))
+        with open(args.out, "w") as f:
+            json.dump(record, f, indent=1)
+            f.write("\n")
+        return
     pr = Producer(cc, pks, stakes, workers)
     pr.pcounts = np.full(args.n, PAYLOAD, np.uint32)
     try:

@@ -22,7 +22,7 @@ Each measurement runs in a fresh child process that loads one library
 (COA_VERIFY_LIB, with its own liblatc.so beside it); parent and new alternate,
 `--pairs` of them, the order within a pair swapped from one pair to the next.
 
-    python tools/runtime_ab.py --parent-lib DIR/libcoa_verify.so --parent-head SHA --new-head SHA
+    python tools/runtime_ab.py --parent-lib DIR/libcoa_verify.so [--new-lib LIB] --parent-head SHA --new-head SHA
 """
 import argparse
 import json
@@ -114,13 +114,15 @@ def main():
     ap.add_argument("--certs", type=int, default=10_000)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--parent-lib")
+    ap.add_argument("--new-lib", default=os.path.join(ROOT, "xrpl-coa-prototype_amd", "lib", "libcoa_verify.so"),
+                    help="the parent's library again measures the parent against itself (the spread to judge by)")
     ap.add_argument("--parent-head")
     ap.add_argument("--new-head")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "runtime_split_ab.json"))
     args = ap.parse_args()
     if args.child:
         return child(args)
-    libs = {"parent": args.parent_lib, "new": os.path.join(ROOT, "xrpl-coa-prototype_amd", "lib", "libcoa_verify.so")}
+    libs = {"parent": args.parent_lib, "new": args.new_lib}
     runs = {"parent": [], "new": []}
     for k in range(args.pairs):
         for which in (("parent", "new"), ("new", "parent"))[k % 2]:  # neither build always runs second

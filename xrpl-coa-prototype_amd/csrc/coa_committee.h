@@ -1,5 +1,6 @@
-// Internal launch wrappers for the committee key cache (f2) and the fused
-// Certificate::verify kernel (f3) -- coa_committee.hip.
+// Internal launch wrappers for the committee key cache (f2, coa_keybuild.hip)
+// and the fused Certificate::verify and message kernels (f3): the throughput
+// variants in coa_committee.hip, the latency variants in coa_cert_lat.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -164,6 +165,8 @@ extern "C" int coa_certificate_verify_many_device_order(
     const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n, size_t n_votes, uint32_t* d_status,
     void* workspace, void* stream, int key_order);
 hipError_t coa_launch_cert_verify(CertArgs a, int lanes_per_sig, uint32_t* pscr, hipStream_t s);
+// the lanes_per_sig == 64 form (k_cert_verify_lat, coa_cert_lat.hip)
+hipError_t coa_launch_cert_verify_lat(CertArgs a, hipStream_t s);
 
 // Header::verify / Vote::verify crypto for many messages (k_msg_verify): one
 // strict signature job per message, the key tables named as in CertArgs.

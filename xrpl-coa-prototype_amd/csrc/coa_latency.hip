@@ -19,7 +19,8 @@
 //     meanwhile wave 0: P = [s]B + [k](-A), verify_strict's small-order test
 //     of R taken on P (an accepting verdict needs R == P), and the half of
 //     the compare that needs only P; wave 1 finishes decompression, compare
-//     and verdict in two row products after its chain (coa_rcmp.h).
+//     and verdict in two row products after its chain (coa_rcmp.h).  The
+//     three roles are coa_lat_job.h's, shared with coa_cert_lat.hip.
 //   key not registered (the halved-scalar check of coa_halved.hip):
 //     wave 0  k, the halving (c, d) with c == d k (mod 8l), e = d s mod l
 //     wave 3  A's decompression (rows), small-order test, table j(-A), j <= 8
@@ -28,8 +29,8 @@
 //     radix-16 Horner chains on the rows, wave 2 [e]B from B's comb; wave 0
 //     sums the three and tests Q == O.
 // Both verdicts are dalek's bit for bit: the cached one by the same argument
-// as k_cert_verify_lat's header job, the uncached one by the halving argument
-// of coa_halved.hip (Q == [d]P exactly, d odd).
+// as k_cert_verify_lat's header job (coa_cert_lat.hip), the uncached one by
+// the halving argument of coa_halved.hip (Q == [d]P exactly, d odd).
 // Batch prefilter (LatArgs::batch, Signature::verify_batch of small calls,
 // crypto/src/lib.rs:206-219): the verdict also requires [l]A == O -- the
 // registered key's flag, or for an unregistered key [l](-A) by wave 0 on
@@ -48,7 +49,7 @@
 #include "coa_halved.h"
 #include "coa_committee.h"
 #include "coa_keycache.h"
-#include "coa_rcmp.h"
+#include "coa_lat_job.h"
 #include "coa_sc.h"
 #include "coa_sha512.h"
 #include "coa_smul.h"
@@ -194,15 +195,12 @@ COA_DEV void horner(ge_p3& out, const uint32_t* tab, const uint32_t* rec, int H,
 COA_DEV void cert_msg(const LatArgs& a, uint32_t item, uint32_t* msg) {
   if (!a.cd_in || item >= a.batch_n) return;
   const uint32_t* src = a.cd_in + (uint64_t)coa_sha::uni(msg[0]) * 18;
-  uint32_t in[18];  // 72-byte records: 8-byte aligned only, so dword loads
+  uint32_t in[18];  // 72-byte records (id, round, origin): 8-byte aligned only, so dword loads
 #pragma unroll
   for (int i = 0; i < 18; i++) in[i] = coa_sha::uni(src[i]);
-  uint64_t st[8];
-  uint32_t h[16];
-  coa_sha::hash_words<18>(st, in);
-  coa_sha::state_to_le_words(h, st);
 #pragma unroll
-  for (int i = 0; i < 8; i++) msg[i] = h[i];
+  for (int i = 0; i < 8; i++) msg[i] = in[i];
+  round_origin_digest(msg, ((uint64_t)in[9] << 32) | in[8], in + 10);
 }
 
 COA_DEV void publish(const LatArgs& a, uint32_t item, bool ok) {
@@ -214,18 +212,8 @@ COA_DEV void publish(const LatArgs& a, uint32_t item, bool ok) {
 // the chain length, d's sign and s < l to sh_meta (lane 0); e stays in `e`
 COA_DEV void halve_item(uint32_t* sh_rec, uint32_t* sh_meta, uint32_t* e_out, const uint32_t* msg,
                         const uint32_t* pk, const uint32_t* rw, const uint32_t* sw, uint32_t lane) {
-  uint64_t st[8];
-  uint32_t h[16], w[24];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    w[i] = rw[i];
-    w[8 + i] = pk[i];
-    w[16 + i] = msg[i];
-  }
-  coa_sha::hash_words<24>(st, w);
-  coa_sha::state_to_le_words(h, st);
   sc k;
-  sc_reduce512(k, h);
+  challenge(k, rw, pk, msg);
   uint32_t c[8], d[8];
   int cost;
   bool neg;
@@ -405,69 +393,30 @@ __global__ void __launch_bounds__(256) k_verify_lat(LatArgs a) {
   load8u(rw, in + 16);
   load8u(sw, in + 24);
   VMARK(0)
-  const int slot = a.nk ? key_lookup_u(a.keys, a.nk, pk) : -1;
+  const int slot = a.nk ? key_lookup<kUniform>(a.keys, a.nk, pk) : -1;
 
-  if (slot >= 0) {  // ------------------------------------------ cached key
-    __shared__ uint32_t s_ready;  // wave 2 published [s]B
+  if (slot >= 0) {  // ------------------------- cached key: the job of coa_lat_job.h
+    __shared__ uint32_t s_ready;  // wave 2 published [s]B (in sh_pt[0])
     __shared__ rcmp::Shared cmp;  // wave 0's half of the compare, for wave 1
-    if (threadIdx.x == 0) {
-      s_ready = 0;
-      cmp.ready = 0;
-    }
-    __syncthreads();
+    latjob::init(&s_ready, cmp);
     if (wave == 1) {  // R's decompression on the rows, the compare, the verdict
-      uint32_t pre = 0;
-      const uint32_t res = rcmp::decompress_eq(cmp, rw, pre);
+      uint32_t word;
+      const bool ok = latjob::decide(cmp, rw, word, [] {}, [] {}) == 0;
+      // a batch-prefilter item also needs a torsion-free key
       const bool tf = item >= a.batch_n || (coa_sha::uni(a.kflags[slot]) & COA_KEY_TORSION_FREE) != 0u;
-      if (lane == 0) publish(a, item, pre == 0 && res == 3u && tf);
+      if (lane == 0) publish(a, item, ok && tf);
       VMARK(3)
-    } else if (wave == 2) {  // [s]B on the rows, published in row-limb layout
-      uint32_t dg[8];
-#pragma unroll
-      for (int i = 0; i < 8; i++) dg[i] = sw[i];
+    } else if (wave == 2) {  // [s]B on the rows
       rp::P1 S;
-      rcmp::comb_sum_rows(S, dg, a.comb, lane);
-      if (lane < 8) {
-        sh_pt[0][lane] = S.X;
-        sh_pt[0][8 + lane] = S.Y;
-        sh_pt[0][16 + lane] = S.Z;
-        sh_pt[0][24 + lane] = S.T;
-      }
-      if (lane == 0) __hip_atomic_store(&s_ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      rcmp::comb_sum_rows(S, sw, a.comb, lane);
+      latjob::publish_sB(sh_pt[0], &s_ready, S, lane);
     } else if (wave == 0) {
-      uint64_t st[8];
-      uint32_t h[16], w[24];
       cert_msg(a, item, msg);
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        w[i] = rw[i];
-        w[8 + i] = pk[i];
-        w[16 + i] = msg[i];
-      }
-      coa_sha::hash_words<24>(st, w);
-      coa_sha::state_to_le_words(h, st);
-      sc k;
-      sc_reduce512(k, h);
-      const uint32_t kf = coa_sha::uni(a.kflags[slot]);
-      const uint32_t pre = (sc_is_canonical(sw) ? 0u : 1u) | ((kf & COA_KEY_DECOMPRESSES) ? 0u : 2u) |
-                           ((kf & COA_KEY_SMALL_ORDER) ? 4u : 0u);
+      uint32_t dg[8];
+      const uint32_t pre = latjob::challenge_bits(dg, rw, pk, sw, msg, coa_sha::uni(a.kflags[slot]), COA_JOB_STRICT);
       rp::P1 P;
-      rcmp::comb_sum_rows(P, k.v, a.ktabs + (uint64_t)slot * COA_KEY_TAB_DWORDS, lane);
-      // everything that needs only P while wave 1 still decompresses R (the
-      // critical chain): P = [s]B + [k](-A) once wave 2 has published [s]B,
-      // verify_strict's small-order test of R taken on P (an accepting
-      // verdict needs R == P, every other verdict is Err already), the
-      // compare's P half
-#pragma unroll 1
-      while (__hip_atomic_load(&s_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)
-        __builtin_amdgcn_s_sleep(1);
-      rp::P1 S;
-      S.X = rp::ld(sh_pt[0]);
-      S.Y = rp::ld(sh_pt[0] + 8);
-      S.Z = rp::ld(sh_pt[0] + 16);
-      S.T = rp::ld(sh_pt[0] + 24);
-      rcmp::add_rows(P, P, S);
-      rcmp::prepare_rows(cmp, P, rw, pre, 8u, lane == 0);
+      rcmp::comb_sum_rows(P, dg, a.ktabs + (uint64_t)slot * COA_KEY_TAB_DWORDS, lane);
+      latjob::finish_P(cmp, sh_pt[0], &s_ready, P, rw, pre, 0, lane);
     }
     VMARK(1)
     return;

@@ -1,6 +1,6 @@
 // Header::verify's worker-id check (primary/src/messages.rs:57-61) on the
 // device: the pieces k_cert_protocol / k_msg_protocol / k_window_verdict
-// (coa_protocol.hip) and k_msg_verdict_lat (coa_committee.hip) share.
+// (coa_protocol.hip) and k_msg_verdict_lat (coa_cert_lat.hip) share.
 #pragma once
 #include "coa_fe.h"
 #include "coa_protocol.h"

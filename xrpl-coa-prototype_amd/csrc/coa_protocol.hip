@@ -62,7 +62,7 @@ COA_DEV uint32_t cert_proto_word(const CertProtArgs& a, const ProtTab& t, uint32
   uint32_t id[8], origin[8];
   load8(id, a.ids + (uint64_t)c * 8);
   load8(origin, a.origins + (uint64_t)c * 8);
-  const int aslot = key_lookup(t.keys, nk, origin);
+  const int aslot = key_lookup<coa_kc::kLane>(t.keys, nk, origin);
   uint32_t id_or = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) id_or |= id[i];
@@ -95,7 +95,7 @@ COA_DEV uint32_t cert_proto_word(const CertProtArgs& a, const ProtTab& t, uint32
     if (live) {
       uint32_t pk[8];
       load8(pk, a.vpks + (v0 + j) * 8);
-      slot = key_lookup(t.keys, nk, pk);
+      slot = key_lookup<coa_kc::kLane>(t.keys, nk, pk);
       if (slot >= 0) atomicMin(&first[slot], (uint32_t)min(j, (uint64_t)0xfffffffeu));
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(64 * kWaves) k_cert_protocol(const CertProtArg
 COA_DEV uint32_t msg_proto_word(const MsgProtArgs& a, const ProtTab& t, uint32_t i) {
   uint32_t author[8];
   load8(author, a.authors + (uint64_t)i * 8);
-  const int slot = key_lookup(t.keys, t.nk, author);
+  const int slot = key_lookup<coa_kc::kLane>(t.keys, t.nk, author);
   uint32_t w = 0;
   if (slot < 0 || t.stake[slot] == 0) {
     w = COA_DAG_UNKNOWN_AUTHOR;

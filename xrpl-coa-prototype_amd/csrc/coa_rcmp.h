@@ -1,6 +1,6 @@
-// decompress(R) == P for the latency kernels (k_verify_lat's and
-// k_cert_verify_lat's registered-key path), with R's decompression fused
-// into the compare.
+// decompress(R) == P for the registered-key latency job (coa_lat_job.h:
+// k_verify_lat in coa_latency.hip and the kernels of coa_cert_lat.hip), with
+// R's decompression fused into the compare.
 //
 // dalek's verify_strict ends with `R == signature_R` after
 // CompressedEdwardsY::decompress (curve25519-dalek 3.x edwards.rs,
@@ -11,7 +11,7 @@
 // everything else moves off it:
 //   * the wave that owns P prepares, while the chain runs, Z_P, Z_P i, the
 //     canonical +-X_P, whether u == 0, and the y half of the compare,
-//     y_R Z_P == Y_P (rcmp::prepare);
+//     y_R Z_P == Y_P (rcmp::prepare_rows);
 //   * after the chain two row products finish everything, the four rows of
 //     the wave each taking one (coa_ge_rows.h): first t^2 and r = u v^3 t,
 //     then w = u v^7 t^2 (check = v r^2 = u w, so check == u, -u, -u i
@@ -65,35 +65,6 @@ COA_DEV bool eq_fe(const fe& a, const fe& b) {
   return e;
 }
 
-// (the wave that owns P; `write` on one lane) the compare's half that needs
-// only P and R's encoding rw; bits travel to the deciding wave unchanged.
-// Sets ready last (release).
-COA_DEV void prepare(Shared& s, const ge_p2& P, const uint32_t* rw, uint32_t bits, bool write) {
-  fe y, yc, yz, i, zi, xc, nx, nxc;
-  fe_from_words(y, rw);
-  fe_mul(yz, y, P.Z);
-  const bool y_eq = fe_eq(yz, P.Y);
-  fe_canon(yc, y);
-  const bool u_zero = eq_one(yc) || eq_m1(yc);  // u = y^2 - 1 == 0
-  fe_const_sqrtm1(i);
-  fe_mul(zi, P.Z, i);
-  fe_canon(xc, P.X);
-  fe_neg(nx, P.X);
-  fe_canon(nxc, nx);
-  if (!write) return;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    s.zp[k] = P.Z.v[k];
-    s.zi[k] = zi.v[k];
-    s.xc[k] = xc.v[k];
-    s.nxc[k] = nxc.v[k];
-  }
-  s.y_eq = y_eq;
-  s.u_zero = u_zero;
-  s.bits = bits;
-  __hip_atomic_store(&s.ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
 // no P to compare with (the key is not registered): only the bits
 COA_DEV void skip(Shared& s, uint32_t bits, bool write) {
   if (!write) return;
@@ -107,10 +78,12 @@ COA_DEV void row_fe(fe& r, uint32_t x, int k) {
   for (int j = 0; j < 8; j++) r.v[j] = __builtin_amdgcn_readlane(x, 16 * k + j);
 }
 
-// P's half for a P in row form (every row holding it): one row product step
+// (the wave that owns P; `write` on one lane) P's half, the part of the compare
+// that needs only P and R's encoding rw, for a P in row form (every row
+// holding it); bits travel to the deciding wave.  One row product step
 // gives X^2, Y^2 (verify_strict's small-order test of R, taken on P: an
 // accepting verdict needs R == P), y_R Z and Z i.  small_bit is OR-ed into
-// bits when P has small order.
+// bits when P has small order.  Sets ready last (release).
 COA_DEV void prepare_rows(Shared& s, const rp::P1& P, const uint32_t* rw, uint32_t bits, uint32_t small_bit,
                           bool write) {
   fe y, i;
@@ -224,9 +197,11 @@ COA_DEV void add_rows(rp::P1& r, const rp::P1& a, const rp::P1& b) {
 }
 
 // (all 64 lanes of the deciding wave) R's decompression and the compare with
-// the P that s describes, once prepare() or skip() has run.  Returns bit 0:
-// decompress(R) is Some; bit 1: decompress(R) == P.  `bits` gets s.bits.
+// the P that s describes, once prepare_rows() or skip() has run.  Returns
+// R_DECOMPRESSES: decompress(R) is Some; R_EQUALS_P: decompress(R) == P.
+// `bits` gets s.bits.
 // chain_done() runs between the power chain and the wait (trace marks).
+constexpr uint32_t R_DECOMPRESSES = 1u, R_EQUALS_P = 2u;
 template <class ChainDone>
 COA_DEV uint32_t decompress_eq(const Shared& s, const uint32_t* rw, uint32_t& bits, ChainDone chain_done) {
   const uint32_t row = __lane_id() >> 4;
@@ -277,10 +252,7 @@ COA_DEV uint32_t decompress_eq(const Shared& s, const uint32_t* rw, uint32_t& bi
 #pragma unroll
   for (int k = 0; k < 8; k++) xp.v[k] = neg ? s.nxc[k] : s.xc[k];
   const bool eq = s.y_eq != 0 && eq_fe(xzc, xp);
-  return (correct || flipped ? 1u : 0u) | (eq ? 2u : 0u);
-}
-COA_DEV uint32_t decompress_eq(const Shared& s, const uint32_t* rw, uint32_t& bits) {
-  return decompress_eq(s, rw, bits, [] {});
+  return (correct || flipped ? R_DECOMPRESSES : 0u) | (eq ? R_EQUALS_P : 0u);
 }
 
 }  // namespace rcmp
