@@ -336,7 +336,8 @@ int coa_committee_register_authorities(const uint8_t* pks, const uint32_t* stake
 #define COA_DAG_REQUIRES_QUORUM 7   /* :208-211 */
 #define COA_DAG_INVALID_VOTES 8     /* :214 */
 #define COA_DAG_VOTES_OPEN 9        /* device-resident form only: every earlier check passed and the votes need
-                                       the exact check (coa_ed25519_verify_batch_groups), as raw status bit 8 */
+                                       the exact check, as raw status bit 8: coa_certificate_votes_resolve_device
+                                       decides it on the device (or coa_ed25519_verify_batch_groups on the host) */
 #define COA_DAG_CODE(v) ((v) & 0xffu)
 #define COA_DAG_VOTE_INDEX(v) ((v) >> 8)
 /* Semantics, exactly the reference's:
@@ -370,9 +371,10 @@ int coa_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const uint
 /* Device-resident forms (asynchronous on `stream`; NULL = the engine's
  * stream): the crypto launch of the *_verify_many_device call, the protocol
  * kernel and the merge, all on `stream`.  d_verdicts[c] may hold
- * COA_DAG_VOTES_OPEN.  `workspace`: NULL (engine-owned; the call then waits
- * for its stream) or at least coa_*_verdict_workspace_bytes bytes of device
- * memory (the crypto call's workspace plus two words per item). */
+ * COA_DAG_VOTES_OPEN (coa_certificate_votes_resolve_device closes it).
+ * `workspace`: NULL (engine-owned; the call then waits for its stream) or at
+ * least coa_*_verdict_workspace_bytes bytes of device memory (the crypto
+ * call's workspace plus two words per item). */
 size_t coa_certificate_verdict_workspace_bytes(size_t n, size_t n_votes);
 int coa_certificate_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
                                         const uint8_t* d_ids, const uint8_t* d_origins, const uint8_t* d_header_sigs,
@@ -380,6 +382,44 @@ int coa_certificate_verdict_many_device(int device, const uint8_t* d_header_data
                                         const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
                                         size_t n_votes, const uint32_t* d_payload_counts, uint32_t* d_verdicts,
                                         void* workspace, void* stream);
+/* Closes the COA_DAG_VOTES_OPEN words of coa_certificate_verdict_many_device
+ * on the device, so a device-resident caller gets the whole of
+ * Certificate::verify without a copy to the host.  The arrays are that call's;
+ * d_verdicts holds its output and is updated in place: every word whose code
+ * is COA_DAG_VOTES_OPEN becomes COA_DAG_OK or COA_DAG_INVALID_VOTES -- exactly
+ * what dalek 1.0.1 verify_batch answers over (Certificate::digest, votes) with
+ * the weights below -- and every other word stays bit for bit.  The call reads
+ * no key cache and needs no registered committee: it is a pure function of its
+ * arguments (the exact random-linear-combination kernels over the open
+ * certificates' votes, found, compacted and counted on the device).
+ *   open_votes_cap  the most open votes the call resolves (0 = n_votes); it
+ *                   sizes the workspace (the term's scratch is 2 KiB per lane,
+ *                   up to 131,072 lanes).  Open certificates are taken in
+ *                   ascending index order while the votes of all of them so
+ *                   far fit; from the first that does not fit on they keep
+ *                   COA_DAG_VOTES_OPEN, and a further call resolves them (a
+ *                   certificate with more votes than the cap never fits it).
+ *   d_zs            n_votes * 16 explicit weights, indexed by a vote's position
+ *                   in d_vote_pks / d_vote_sigs (the parity form of
+ *                   coa_cpu_certificate_verify_many_z), or NULL: derived on the
+ *                   device from rng_seed (0 = fresh OS entropy per call, drawn
+ *                   on the host) by coa_ed25519_verify_batch's block with the
+ *                   certificate's index as the group and the vote's position
+ *                   in the call as i -- independent of which other
+ *                   certificates are open and of open_votes_cap
+ *   d_counts        NULL, or three words: open certificates found, open
+ *                   certificates resolved, open votes resolved
+ * `workspace`: at least coa_certificate_votes_resolve_workspace_bytes(n,
+ * n_votes, open_votes_cap) bytes of device memory -- the call then only
+ * enqueues on `stream` (no host synchronisation, no copy, no allocation) -- or
+ * NULL: engine-owned, and the call waits for its stream.  n = 0 returns
+ * COA_OK; a null array COA_EINVAL. */
+size_t coa_certificate_votes_resolve_workspace_bytes(size_t n, size_t n_votes, size_t open_votes_cap);
+int coa_certificate_votes_resolve_device(int device, const uint8_t* d_ids, const uint8_t* d_origins,
+                                         const uint64_t* d_rounds, const uint8_t* d_vote_pks,
+                                         const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
+                                         size_t n_votes, size_t open_votes_cap, const uint8_t* d_zs, uint64_t rng_seed,
+                                         uint32_t* d_verdicts, uint32_t* d_counts, void* workspace, void* stream);
 size_t coa_message_verdict_workspace_bytes(size_t n);
 int coa_header_verdict_many_device(int device, const uint8_t* d_header_data, const uint64_t* d_header_offsets,
                                    const uint8_t* d_ids, const uint8_t* d_authors, const uint8_t* d_sigs, size_t n,

@@ -203,6 +203,13 @@ extern "C" {
                                                n_votes: usize, d_payload_counts: *const u32,
                                                d_verdicts: *mut u32, workspace: *mut c_void,
                                                stream: *mut c_void) -> c_int;
+    pub fn coa_certificate_votes_resolve_workspace_bytes(n: usize, n_votes: usize, open_votes_cap: usize) -> usize;
+    pub fn coa_certificate_votes_resolve_device(device: c_int, d_ids: *const u8, d_origins: *const u8,
+                                                d_rounds: *const u64, d_vote_pks: *const u8,
+                                                d_vote_sigs: *const u8, d_vote_offsets: *const u64, n: usize,
+                                                n_votes: usize, open_votes_cap: usize, d_zs: *const u8,
+                                                rng_seed: u64, d_verdicts: *mut u32, d_counts: *mut u32,
+                                                workspace: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn coa_message_verdict_workspace_bytes(n: usize) -> usize;
     pub fn coa_header_verdict_many_device(device: c_int, d_header_data: *const u8, d_header_offsets: *const u64,
                                           d_ids: *const u8, d_authors: *const u8, d_sigs: *const u8, n: usize,

@@ -169,6 +169,9 @@ def lib():
         "coa_certificate_verdict_workspace_bytes": ([sz, sz], sz),
         "coa_certificate_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp,
                                                  vp], ctypes.c_int),
+        "coa_certificate_votes_resolve_workspace_bytes": ([sz, sz, sz], sz),
+        "coa_certificate_votes_resolve_device": ([ctypes.c_int, vp, vp, vp, vp, vp, vp, sz, sz, sz, vp, ctypes.c_uint64,
+                                                  vp, vp, vp, vp], ctypes.c_int),
         "coa_message_verdict_workspace_bytes": ([sz], sz),
         "coa_header_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp], ctypes.c_int),
         "coa_vote_verdict_many_device": ([ctypes.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp], ctypes.c_int),
@@ -950,6 +953,28 @@ def certificate_verdict_many_device(device, hdata, hoff, ids, origins, hsigs, ro
                                                      vpks.data_ptr(), vsigs.data_ptr(), voff.data_ptr(), ids.shape[0],
                                                      vpks.shape[0], pcounts.data_ptr(), verdicts.data_ptr(), ws,
                                                      _handle(device, stream)))
+
+
+def certificate_votes_resolve_workspace_bytes(n, n_votes, open_votes_cap=0):
+    return lib().coa_certificate_votes_resolve_workspace_bytes(n, n_votes, open_votes_cap)
+
+
+def certificate_votes_resolve_device(device, ids, origins, rounds, vpks, vsigs, voff, verdicts, zs=None, rng_seed=0,
+                                     open_votes_cap=0, counts=None, stream=None, workspace=None):
+    """Closes the DAG_VOTES_OPEN words certificate_verdict_many_device left in
+    `verdicts` (uint32 tensor [n], updated in place) on the device: DAG_OK or
+    DAG_INVALID_VOTES, dalek's verify_batch over (Certificate::digest, votes).
+    zs: uint8 tensor [n_votes, 16] of explicit weights, else derived from
+    rng_seed (0 = OS entropy).  counts: None or a uint32 tensor [3] (open
+    found, open resolved, open votes resolved).  Enqueued on `stream`."""
+    ws = workspace.data_ptr() if workspace is not None else None
+    _check(lib().coa_certificate_votes_resolve_device(device, ids.data_ptr(), origins.data_ptr(), rounds.data_ptr(),
+                                                      vpks.data_ptr(), vsigs.data_ptr(), voff.data_ptr(), ids.shape[0],
+                                                      vpks.shape[0], open_votes_cap,
+                                                      zs.data_ptr() if zs is not None else None, rng_seed,
+                                                      verdicts.data_ptr(),
+                                                      counts.data_ptr() if counts is not None else None, ws,
+                                                      _handle(device, stream)))
 
 
 def header_verdict_many_device(device, hdata, hoff, ids, authors, sigs, pcounts, verdicts, stream=None,

@@ -8,6 +8,8 @@
 #include <cstring>
 
 #include "coa_protocol_dev.h"
+#include "coa_resolve.h"
+#include "coa_resolve_ws.h"
 
 namespace coa_rt __attribute__((visibility("hidden"))) {
 
@@ -1120,6 +1122,46 @@ int coa_certificate_verdict_many_device(int device, const uint8_t* d_header_data
                                      d_vote_pks, d_vote_sigs, d_vote_offsets, n, n_votes);
         return coa_launch_cert_protocol(cert_prot_args(a, d_payload_counts, pw), t, s);
       });
+}
+
+size_t coa_certificate_votes_resolve_workspace_bytes(size_t n, size_t n_votes, size_t open_votes_cap) {
+  return ResolveWs(n, n_votes, open_votes_cap).bytes;
+}
+
+int coa_certificate_votes_resolve_device(int device, const uint8_t* d_ids, const uint8_t* d_origins,
+                                         const uint64_t* d_rounds, const uint8_t* d_vote_pks,
+                                         const uint8_t* d_vote_sigs, const uint64_t* d_vote_offsets, size_t n,
+                                         size_t n_votes, size_t open_votes_cap, const uint8_t* d_zs, uint64_t rng_seed,
+                                         uint32_t* d_verdicts, uint32_t* d_counts, void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  if (!d_ids || !d_origins || !d_rounds || !d_vote_offsets || !d_verdicts || (n_votes && (!d_vote_pks || !d_vote_sigs)))
+    return fail(COA_EINVAL, "null argument");
+  if (check_n(n + n_votes) != COA_OK) return COA_EINVAL;
+  const int rc = ensure_init();
+  if (rc != COA_OK) return rc;
+  Dev* d;
+  hipStream_t s;
+  if (const int e = enter_device(device, stream, d, s)) return e;
+  ResolveArgs a{};
+  a.ids = reinterpret_cast<const uint32_t*>(d_ids);
+  a.origins = reinterpret_cast<const uint32_t*>(d_origins);
+  a.rounds = d_rounds;
+  a.vpks = d_vote_pks;
+  a.vsigs = d_vote_sigs;
+  a.voff = d_vote_offsets;
+  a.zs = reinterpret_cast<const uint32_t*>(d_zs);
+  // derived weights: OS entropy is drawn here, on the host, and only passed on
+  a.seed = d_zs ? 0 : (rng_seed ? rng_seed : os_entropy_seed());
+  a.n = (uint32_t)n;
+  a.n_votes = (uint32_t)n_votes;
+  a.cap = (uint32_t)std::min(open_votes_cap, n_votes);  // 0 and n_votes both mean every vote
+  a.verdicts = d_verdicts;
+  a.counts_out = d_counts;
+  // no key-cache generation to trail: the call reads no committee table
+  return with_workspace(*d, s, workspace, d->vws, ResolveWs(n, n_votes, a.cap).bytes, nullptr, [&](void* ws) -> int {
+    HIP_TRY(coa_launch_votes_resolve(a, static_cast<uint8_t*>(ws), d->btab, s));
+    return COA_OK;
+  });
 }
 
 size_t coa_message_verdict_workspace_bytes(size_t n) { return verdict_ws_bytes(coa_message_workspace_bytes(n), n); }
