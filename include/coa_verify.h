@@ -467,6 +467,91 @@ int coa_wire_decode_headers(const uint8_t* frames, const uint64_t* frame_offsets
                             uint64_t* header_offsets, uint8_t* ids, uint8_t* authors, uint8_t* sigs,
                             uint64_t* rounds, uint32_t* payload_counts);
 
+/* ---------------------------------------- wire decode on the device (f4)
+ * The same decode with the frames in device memory, bit-identical to the
+ * host decoder above, written straight into the arrays of the *_many_device
+ * calls.  d_frames[d_frame_offsets[i] .. d_frame_offsets[i+1]) is frame i;
+ * frame_bytes is the size of d_frames.  A frame whose range is not inside
+ * [0, frame_bytes), or whose offsets decrease, is COA_WIRE_ETRUNC and none of
+ * its bytes are read; no length prefix is trusted before it has been checked
+ * against the frame's end.
+ *
+ * Three passes, all enqueued on `stream`: a scan (one wavefront per frame:
+ * kind or error, digest-input length 40 + 36 |distinct payload keys| + 32
+ * |distinct parents|, vote and payload counts), exclusive prefix sums of the
+ * header bytes and votes (block totals, a scan of the totals, the add: three
+ * launches, no kernel waits for another workgroup), and the decode and
+ * scatter.
+ *
+ * The decode calls are index-aligned with the frames: item i belongs to
+ * frame i.  Where frame i is a valid message of the call's kind every output
+ * equals the host decoder's for that frame and d_kinds[i] is the kind.  For
+ * any other frame d_kinds[i] is what the scan says -- another kind, a negative
+ * COA_WIRE_E*, or COA_WIRE_ECAPACITY -- and item i is an empty placeholder:
+ * zeroed id, keys, signature, round and payload count, no header bytes and no
+ * votes (offsets[i+1] == offsets[i]).  The caller reads d_kinds before it
+ * trusts item i.  Sorting frames into per-kind batches is the caller's: it
+ * needs a frame's first four bytes only and no decode.
+ *   COA_WIRE_ECAPACITY  a Header or Certificate frame the host decoder
+ *       accepts whose wire count of payload entries or of parents exceeds
+ *       COA_WIRE_DEV_MAX_ENTRIES (every host error takes precedence); the
+ *       caller decodes such a frame on the host.  Votes are not sorted and
+ *       have no cap.
+ *   d_header_offsets[0] = d_vote_offsets[0] = 0.
+ *   d_totals: four words -- header bytes, votes, frames decoded as the call's
+ *       kind, frames not decoded as it.
+ * Output capacities are the caller's to provide: d_header_data frame_bytes +
+ * 16 bytes (a digest input is never longer than its frame, and the verify
+ * kernels read up to 16 bytes past the last input), the vote arrays
+ * COA_WIRE_VOTES_BOUND(frame_bytes) entries, every per-frame array n (offsets
+ * n + 1).  Outputs must not alias the frames.
+ * `workspace`: at least coa_wire_workspace_bytes(n, frame_bytes) bytes of
+ * device memory -- the call then only enqueues (no host synchronisation, no
+ * copy, no allocation) -- or NULL: engine-owned, and the call waits for its
+ * stream.  n = 0 returns COA_OK; a null required array or an n or frame_bytes
+ * too large for one call COA_EINVAL; no device COA_ENODEVICE.
+ * coa_wire_scan_device: d_header_bytes and d_votes are optional. */
+#define COA_WIRE_ECAPACITY (-13)
+#define COA_WIRE_DEV_MAX_ENTRIES 1024 /* per set: payload entries, parents */
+#define COA_WIRE_VOTES_BOUND(frame_bytes) ((frame_bytes) / 115) /* 8 + 43 + 64: the shortest vote that decodes */
+size_t coa_wire_workspace_bytes(size_t n, size_t frame_bytes);
+int coa_wire_scan_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                         size_t frame_bytes, int32_t* d_kinds, uint64_t* d_header_bytes, uint64_t* d_votes,
+                         void* workspace, void* stream);
+int coa_wire_decode_certificates_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                                        size_t frame_bytes, uint8_t* d_header_data, uint64_t* d_header_offsets,
+                                        uint8_t* d_ids, uint8_t* d_origins, uint8_t* d_header_sigs, uint64_t* d_rounds,
+                                        uint8_t* d_vote_pks, uint8_t* d_vote_sigs, uint64_t* d_vote_offsets,
+                                        uint32_t* d_payload_counts, int32_t* d_kinds, uint64_t* d_totals,
+                                        void* workspace, void* stream);
+int coa_wire_decode_headers_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                                   size_t frame_bytes, uint8_t* d_header_data, uint64_t* d_header_offsets,
+                                   uint8_t* d_ids, uint8_t* d_authors, uint8_t* d_sigs, uint32_t* d_payload_counts,
+                                   uint64_t* d_rounds, int32_t* d_kinds, uint64_t* d_totals, void* workspace,
+                                   void* stream);
+int coa_wire_decode_votes_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                                 size_t frame_bytes, uint8_t* d_ids, uint64_t* d_rounds, uint8_t* d_origins,
+                                 uint8_t* d_authors, uint8_t* d_sigs, int32_t* d_kinds, uint64_t* d_totals,
+                                 void* workspace, void* stream);
+/* Frames to verdicts, host pointers: the drop-in for "dispatch, then verify".
+ * One H2D of the frames and their offsets through the engine's page-locked
+ * staging, the device decode, the *_verdict_many_device call over the decoded
+ * arrays (for certificates followed by coa_certificate_votes_resolve_device,
+ * so no COA_DAG_VOTES_OPEN remains) and one D2H of kinds and words, on one
+ * context.  kinds_out[i] is the scan's answer for frame i; where it is not the
+ * call's kind verdicts_out[i] = COA_DAG_NO_MESSAGE.  The certificate form reads
+ * d_totals back (32 bytes) between the decode and the verdict call, which
+ * takes its vote count as a host argument.  rng_seed as
+ * coa_certificate_verdict_many.  A generation without a protocol table gives
+ * COA_EINVAL, as for the verdict calls. */
+#define COA_DAG_NO_MESSAGE 255u /* fused calls: frame i is not a decodable message of the call's kind */
+int coa_wire_certificate_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n,
+                                      uint64_t rng_seed, int32_t* kinds_out, uint32_t* verdicts_out);
+int coa_wire_header_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, int32_t* kinds_out,
+                                 uint32_t* verdicts_out);
+int coa_wire_vote_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, int32_t* kinds_out,
+                               uint32_t* verdicts_out);
+
 /* --------------------------------------------------------------- signing
  * RFC 8032 signing == crypto::Signature::new (crypto/src/lib.rs:185-191) /
  * generate_keypair (:167-175) from 32-byte seeds.  Not on the verification

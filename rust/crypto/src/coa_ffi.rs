@@ -234,6 +234,36 @@ extern "C" {
                                    header_offsets: *mut u64, ids: *mut u8, authors: *mut u8, sigs: *mut u8,
                                    rounds: *mut u64, payload_counts: *mut u32) -> c_int;
 
+    // ------------------------------------- wire decode on the device (f4)
+    pub fn coa_wire_workspace_bytes(n: usize, frame_bytes: usize) -> usize;
+    pub fn coa_wire_scan_device(device: c_int, d_frames: *const u8, d_frame_offsets: *const u64, n: usize,
+                                frame_bytes: usize, d_kinds: *mut i32, d_header_bytes: *mut u64,
+                                d_votes: *mut u64, workspace: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn coa_wire_decode_certificates_device(device: c_int, d_frames: *const u8, d_frame_offsets: *const u64,
+                                               n: usize, frame_bytes: usize, d_header_data: *mut u8,
+                                               d_header_offsets: *mut u64, d_ids: *mut u8, d_origins: *mut u8,
+                                               d_header_sigs: *mut u8, d_rounds: *mut u64, d_vote_pks: *mut u8,
+                                               d_vote_sigs: *mut u8, d_vote_offsets: *mut u64,
+                                               d_payload_counts: *mut u32, d_kinds: *mut i32, d_totals: *mut u64,
+                                               workspace: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn coa_wire_decode_headers_device(device: c_int, d_frames: *const u8, d_frame_offsets: *const u64, n: usize,
+                                          frame_bytes: usize, d_header_data: *mut u8, d_header_offsets: *mut u64,
+                                          d_ids: *mut u8, d_authors: *mut u8, d_sigs: *mut u8,
+                                          d_payload_counts: *mut u32, d_rounds: *mut u64, d_kinds: *mut i32,
+                                          d_totals: *mut u64, workspace: *mut c_void,
+                                          stream: *mut c_void) -> c_int;
+    pub fn coa_wire_decode_votes_device(device: c_int, d_frames: *const u8, d_frame_offsets: *const u64, n: usize,
+                                        frame_bytes: usize, d_ids: *mut u8, d_rounds: *mut u64, d_origins: *mut u8,
+                                        d_authors: *mut u8, d_sigs: *mut u8, d_kinds: *mut i32, d_totals: *mut u64,
+                                        workspace: *mut c_void, stream: *mut c_void) -> c_int;
+    // frames to verdicts: the drop-in for "dispatch, then verify"
+    pub fn coa_wire_certificate_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, rng_seed: u64,
+                                             kinds_out: *mut i32, verdicts_out: *mut u32) -> c_int;
+    pub fn coa_wire_header_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, kinds_out: *mut i32,
+                                        verdicts_out: *mut u32) -> c_int;
+    pub fn coa_wire_vote_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, kinds_out: *mut i32,
+                                      verdicts_out: *mut u32) -> c_int;
+
     // ----------------------------------------------------------- signing
     pub fn coa_ed25519_public_keys(seeds: *const u8, n: usize, pks_out: *mut u8) -> c_int;
     pub fn coa_ed25519_sign_many(seeds: *const u8, msgs: *const u8, msg_len: usize, n: usize, pks_out: *mut u8,

@@ -150,6 +150,14 @@ def lib():
         "coa_wire_decode_votes": ([P8, P64, sz, P8, P64, P8, P8, P8], ctypes.c_int),
         "coa_wire_decode_headers": ([P8, P64, sz, P8, P64, P8, P8, P8, P64, ctypes.POINTER(ctypes.c_uint32)],
                                     ctypes.c_int),
+        "coa_wire_workspace_bytes": ([sz, sz], sz),
+        "coa_wire_scan_device": ([ctypes.c_int, vp, vp, sz, sz, vp, vp, vp, vp, vp], ctypes.c_int),
+        "coa_wire_decode_certificates_device": ([ctypes.c_int, vp, vp, sz, sz] + [vp] * 14, ctypes.c_int),
+        "coa_wire_decode_headers_device": ([ctypes.c_int, vp, vp, sz, sz] + [vp] * 11, ctypes.c_int),
+        "coa_wire_decode_votes_device": ([ctypes.c_int, vp, vp, sz, sz] + [vp] * 9, ctypes.c_int),
+        "coa_wire_certificate_verdict_many": ([P8, P64, sz, ctypes.c_uint64, vp, vp], ctypes.c_int),
+        "coa_wire_header_verdict_many": ([P8, P64, sz, vp, vp], ctypes.c_int),
+        "coa_wire_vote_verdict_many": ([P8, P64, sz, vp, vp], ctypes.c_int),
         # the engine's own CPU path (explicit only; never a silent fallback)
         "coa_cpu_ed25519_verify_strict": ([P8, sz, P8, P8], ctypes.c_int),
         "coa_cpu_ed25519_verify_strict_many": ([P8, sz, P8, P8, sz, P8, ctypes.c_int], ctypes.c_int),
@@ -1114,6 +1122,97 @@ def wire_decode_headers(frames):
                                          pc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
     return {"header_inputs": [bytes(hd[int(hoff[i]):int(hoff[i + 1])]) for i in range(n)], "ids": ids,
             "authors": authors, "sigs": sigs, "rounds": rounds, "payload_counts": pc[:n]}
+
+
+# ------------------------------------------------- wire on the device (f4)
+WIRE_ECAPACITY = -13
+WIRE_DEV_MAX_ENTRIES = 1024
+DAG_NO_MESSAGE = 255
+
+
+def wire_votes_bound(frame_bytes):
+    """COA_WIRE_VOTES_BOUND: entries the vote arrays of a device decode need."""
+    return frame_bytes // 115
+
+
+def wire_workspace_bytes(n, frame_bytes):
+    return lib().coa_wire_workspace_bytes(n, frame_bytes)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def wire_scan_device(device, frames, offsets, kinds, header_bytes=None, votes=None, frame_bytes=None, stream=None,
+                     workspace=None):
+    """Frames in device memory (torch tensors: frames uint8, offsets uint64/int64
+    [n + 1]) -> kinds (int32 [n]: MSG_*, negative WIRE_E* or WIRE_ECAPACITY) and,
+    if given, header digest input bytes and vote counts (int64 [n]).
+    frame_bytes: the frames' size (default: the tensor's).  Enqueued on `stream`."""
+    fb = frames.shape[0] if frame_bytes is None else frame_bytes
+    _check(lib().coa_wire_scan_device(device, frames.data_ptr(), offsets.data_ptr(), kinds.shape[0], fb,
+                                      kinds.data_ptr(), _ptr(header_bytes), _ptr(votes), _ptr(workspace),
+                                      _handle(device, stream)))
+
+
+def wire_decode_certificates_device(device, frames, offsets, hdata, hoff, ids, origins, hsigs, rounds, vpks, vsigs,
+                                    voff, pcounts, kinds, totals, frame_bytes=None, stream=None, workspace=None):
+    """Frames in device memory -> the arrays of certificate_verdict_many_device,
+    index-aligned with the frames: item i is frame i's certificate where
+    kinds[i] == MSG_CERTIFICATE and an empty placeholder elsewhere.  Capacities:
+    hdata frame_bytes + 16, vpks / vsigs wire_votes_bound(frame_bytes) rows.
+    totals (int64 [4]): header bytes, votes, decoded, not decoded."""
+    fb = frames.shape[0] if frame_bytes is None else frame_bytes
+    _check(lib().coa_wire_decode_certificates_device(
+        device, frames.data_ptr(), offsets.data_ptr(), kinds.shape[0], fb, hdata.data_ptr(), hoff.data_ptr(),
+        ids.data_ptr(), origins.data_ptr(), hsigs.data_ptr(), rounds.data_ptr(), vpks.data_ptr(), vsigs.data_ptr(),
+        voff.data_ptr(), pcounts.data_ptr(), kinds.data_ptr(), totals.data_ptr(), _ptr(workspace),
+        _handle(device, stream)))
+
+
+def wire_decode_headers_device(device, frames, offsets, hdata, hoff, ids, authors, sigs, pcounts, rounds, kinds, totals,
+                               frame_bytes=None, stream=None, workspace=None):
+    """The arrays of header_verdict_many_device (+ rounds, kinds, totals)."""
+    fb = frames.shape[0] if frame_bytes is None else frame_bytes
+    _check(lib().coa_wire_decode_headers_device(
+        device, frames.data_ptr(), offsets.data_ptr(), kinds.shape[0], fb, hdata.data_ptr(), hoff.data_ptr(),
+        ids.data_ptr(), authors.data_ptr(), sigs.data_ptr(), pcounts.data_ptr(), rounds.data_ptr(), kinds.data_ptr(),
+        totals.data_ptr(), _ptr(workspace), _handle(device, stream)))
+
+
+def wire_decode_votes_device(device, frames, offsets, ids, rounds, origins, authors, sigs, kinds, totals,
+                             frame_bytes=None, stream=None, workspace=None):
+    """The arrays of vote_verdict_many_device (+ kinds, totals)."""
+    fb = frames.shape[0] if frame_bytes is None else frame_bytes
+    _check(lib().coa_wire_decode_votes_device(
+        device, frames.data_ptr(), offsets.data_ptr(), kinds.shape[0], fb, ids.data_ptr(), rounds.data_ptr(),
+        origins.data_ptr(), authors.data_ptr(), sigs.data_ptr(), kinds.data_ptr(), totals.data_ptr(), _ptr(workspace),
+        _handle(device, stream)))
+
+
+def _wire_verdicts(call, frames, *seed):
+    n = len(frames)
+    data, offs = _frames(frames)
+    kinds = np.zeros(max(n, 1), np.int32)
+    words = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(call(_u8p(data), _u64p(offs), n, *seed, _u8p(kinds), _u8p(words)))
+    return kinds[:n], words[:n]
+
+
+def wire_certificate_verdict_many(frames, rng_seed=0):
+    """Raw PrimaryMessage frames -> (kinds int32 [n], DAG_* words uint32 [n]):
+    the device decode, Certificate::verify's verdict and the resolution of open
+    votes in one call; DAG_NO_MESSAGE where a frame is not a decodable
+    Certificate (kinds says what it is)."""
+    return _wire_verdicts(lib().coa_wire_certificate_verdict_many, frames, rng_seed)
+
+
+def wire_header_verdict_many(frames):
+    return _wire_verdicts(lib().coa_wire_header_verdict_many, frames)
+
+
+def wire_vote_verdict_many(frames):
+    return _wire_verdicts(lib().coa_wire_vote_verdict_many, frames)
 
 
 # --------------------------------------------------------- aggregation queue
