@@ -9,8 +9,9 @@ comes from the kernels under test.
 
 The frames sit in a device buffer with 4 KiB of slack behind them and
 frame_bytes is the true size, so a wrong bound reads allocated memory and
-shows as a wrong answer.  Out-of-range and decreasing offsets are exercised on
-the CPU only (tests/test_wire_parse_host.py).
+shows as a wrong answer.  The kernels' work split at its own boundaries
+(alignment, the staging switch, the prefix sums, output extents, the offsets
+rule) is tests/test_gpu_wire_device_edges.py.
 
 Header cases of verdict_cases.py whose digest input no frame can carry (random
 bytes: it does not start with the author, or its sets are not in key order) go
@@ -49,30 +50,68 @@ def _np(t, dtype=None):
     return a.view(dtype) if dtype is not None else a
 
 
-def device_decode(e, kind, frames, own=False):
+GUARD = 256
+BYTE_ARRAYS = ("hdata", "ids", "authors", "origins", "sigs", "vpks", "vsigs")
+
+
+def device_decode(e, kind, frames, own=False, guard=False, shift=0, frames_shift=0, offsets=None, slack=None):
     """One coa_wire_decode_*_device call over `frames`; every output as numpy.
-    own: a caller workspace, on a stream that is not the default one."""
+    own: a caller workspace, on a stream that is not the default one.
+    guard: every output and a caller workspace of exactly
+    wire_workspace_bytes lie inside larger allocations, GUARD pattern bytes
+    before and after each, and are of exactly the capacities the call states
+    (hdata frame_bytes + 16, vpks / vsigs wire_votes_bound rows);
+    out["bands"] names every array whose bands the call changed.
+    shift: the byte arrays start this many bytes into their allocation.
+    frames_shift: the frames tensor is a view this many bytes into its allocation.
+    offsets: the frame offsets (default: the frames back to back); `frames` is
+    then the buffer's content in order, n = len(offsets) - 1.
+    slack: what lies behind frame_bytes (default SLACK bytes of 0xee)."""
     import torch
 
-    n = len(frames)
     blob = b"".join(frames)
     fb = len(blob)
-    d_frames = _dev(np.frombuffer(blob + b"\xee" * SLACK, np.uint8))
-    offs = np.zeros(n + 1, np.uint64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
+    if offsets is None:
+        offs = np.zeros(len(frames) + 1, np.uint64)
+        offs[1:] = np.cumsum([len(f) for f in frames])
+    else:
+        offs = np.array(offsets, np.uint64)
+        assert int(offs.max()) <= fb + SLACK  # inside the allocation
+    n = len(offs) - 1
+    tail = (slack or b"") + b"\xee" * (SLACK - len(slack or b""))
+    assert len(tail) == SLACK
+    d_frames = _dev(np.frombuffer(b"\xdd" * frames_shift + blob + tail, np.uint8))[frames_shift:]
     d_offs = _dev(offs)
     dev = torch.device("cuda", 0)
-    fill = lambda shape, dt: torch.full(shape, 0x5a, dtype=dt, device=dev)  # noqa: E731
-    nvb = max(e.wire_votes_bound(fb), 1)
-    o = dict(hdata=fill((fb + 16 + SLACK,), torch.uint8), hoff=fill((n + 1,), torch.int64), ids=fill((n, 32), torch.uint8),
-             authors=fill((n, 32), torch.uint8), origins=fill((n, 32), torch.uint8), sigs=fill((n, 64), torch.uint8),
-             rounds=fill((n,), torch.int64), pcounts=fill((n,), torch.int32), vpks=fill((nvb, 32), torch.uint8),
-             vsigs=fill((nvb, 64), torch.uint8), voff=fill((n + 1,), torch.int64), kinds=fill((n,), torch.int32),
-             totals=fill((4,), torch.int64))
+    raw = {}
+
+    def fill(name, shape, dt, exact=None):
+        if not guard and not (shift and name in BYTE_ARRAYS):
+            return torch.full(shape, 0x5a, dtype=dt, device=dev)
+        if guard and exact is not None:
+            shape = exact
+        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+        lo = (GUARD if guard else 0) + (shift if name in BYTE_ARRAYS else 0)
+        buf = torch.full((lo + nbytes + GUARD,), 0x5a, dtype=torch.uint8, device=dev)
+        raw[name] = (buf, lo, nbytes)
+        return buf[lo:lo + nbytes].view(dt).view(shape)
+
+    nvb = e.wire_votes_bound(fb)
+    o = dict(hdata=fill("hdata", (fb + 16 + SLACK,), torch.uint8, (fb + 16,)), hoff=fill("hoff", (n + 1,), torch.int64),
+             ids=fill("ids", (n, 32), torch.uint8), authors=fill("authors", (n, 32), torch.uint8),
+             origins=fill("origins", (n, 32), torch.uint8), sigs=fill("sigs", (n, 64), torch.uint8),
+             rounds=fill("rounds", (n,), torch.int64), pcounts=fill("pcounts", (n,), torch.int32),
+             vpks=fill("vpks", (max(nvb, 1), 32), torch.uint8, (nvb, 32)),
+             vsigs=fill("vsigs", (max(nvb, 1), 64), torch.uint8, (nvb, 64)), voff=fill("voff", (n + 1,), torch.int64),
+             kinds=fill("kinds", (n,), torch.int32), totals=fill("totals", (4,), torch.int64))
     kw = {}
     side = None
-    if own:
-        ws = torch.empty(max(e.wire_workspace_bytes(n, fb), 16), dtype=torch.uint8, device=dev)
+    if own or guard:
+        if guard:
+            ws = fill("workspace", (e.wire_workspace_bytes(n, fb),), torch.uint8)
+            assert ws.data_ptr() % 256 == 0
+        else:
+            ws = torch.empty(max(e.wire_workspace_bytes(n, fb), 16), dtype=torch.uint8, device=dev)
         side = torch.cuda.Stream(device=0)
         side.wait_stream(torch.cuda.current_stream(0))
         kw = dict(stream=side, workspace=ws)
@@ -96,6 +135,8 @@ def device_decode(e, kind, frames, own=False):
     out["pcounts"] = out["pcounts"].view(np.uint32)
     out["tensors"] = o
     out["frame_bytes"] = fb
+    out["bands"] = [k for k, (buf, lo, nbytes) in raw.items()
+                    if not (bool((buf[:lo] == 0x5a).all()) and bool((buf[lo + nbytes:] == 0x5a).all()))]
     return out
 
 
