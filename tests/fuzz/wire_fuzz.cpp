@@ -1,5 +1,6 @@
 // Mutation fuzzer of the native bincode decoder (xrpl-coa-prototype_amd/csrc/
-// coa_wire.cpp), built with -fsanitize=address,undefined: the decoder parses
+// coa_wire.cpp and, through it, the frame grammar csrc/coa_wire_parse.h that it
+// drives), built with -fsanitize=address,undefined: the decoder parses
 // untrusted network frames (the bytes PrimaryReceiverHandler::dispatch
 // receives, primary/src/primary.rs:223-244), so every out-of-bounds read,
 // overflow or UB on malformed input must be caught here.

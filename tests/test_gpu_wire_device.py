@@ -3,7 +3,9 @@ frames-to-verdicts calls (coa_wire_*_verdict_many).
 
 Expected fields come from the independent encoder tests/wire_codec.py (the
 fields a frame was built from, header_digest_input) and from the host decoder
-coa_wire.cpp, which tests/test_wire.py pins against that encoder; expected
+coa_wire.cpp -- the sequential driver of the rules the kernels split over
+lanes (coa_wire_parse.h), which tests/test_wire.py pins against that encoder
+and tests/test_wire_parse_host.py against an independent model; expected
 verdict words from tests/verdict_cases.py and the oracle.  Nothing expected
 comes from the kernels under test.
 

@@ -10,7 +10,10 @@ extents of every output (E), the offsets rule (F), a seeded batch of mutated
 frames (G) and the fused calls' reused buffers (H).
 
 Everything is compared bit for bit.  Expected fields come from the host decoder
-coa_wire.cpp and the independent encoder tests/wire_codec.py (check_decode of
+coa_wire.cpp (the same rules of coa_wire_parse.h run one after the other, so a
+difference is one of the work split; the rules themselves are pinned against
+an independent model in tests/test_wire_parse_host.py) and the independent
+encoder tests/wire_codec.py (check_decode of
 tests/test_gpu_wire_device.py); expected verdict words from the host route
 wire_scan + wire_decode_* + *_verdict_many.  Nothing expected comes from the
 kernels under test.  What these inputs must be for the tests to mean anything

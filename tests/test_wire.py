@@ -1,4 +1,5 @@
-"""Wire decode of PrimaryMessage frames (coa_wire.cpp).
+"""Wire decode of PrimaryMessage frames (coa_wire.cpp, the host's sequential
+driver of the grammar coa_wire_parse.h).
 
 CPU: frames built by an independent encoder (tests/wire_codec.py, from the
 reference's serde derives) decode to exactly the fields and the
@@ -112,6 +113,7 @@ def test_truncation_and_malformed_keys():
         "unpadded": (W.raw_key(base64.b64encode(k32).rstrip(b"=")), k32),
         "longer key, first 32 bytes kept": (W.raw_key(base64.b64encode(k32 + b"tail!!")), k32),
         "short key (reference panics)": (W.raw_key(base64.b64encode(k32[:16])), None),
+        "one byte short, of the canonical length": (W.raw_key(base64.b64encode(k32[:31])), None),
         "invalid character": (W.raw_key(base64.b64encode(k32)[:-3] + b"*A="), None),
         "non-zero trailing bits": (W.raw_key(base64.b64encode(k32)[:-2] + b"B="), None),
         "too much padding": (W.raw_key(base64.b64encode(k32) + b"=="), None),

@@ -1,5 +1,6 @@
 """CPU: the premises of tests/test_gpu_wire_device_edges.py, asserted with the
-host decoder coa_wire.cpp alone.
+host decoder coa_wire.cpp alone (the sequential driver of coa_wire_parse.h, the
+grammar the kernels share).
 
 Those GPU tests pin the device wire decoder's work split (LDS staging, the two
 compiled bodies, the speculation on the vote stride, the lane-strided sort,

@@ -1,12 +1,17 @@
 """CPU: the device wire decoder's host side.
 
-The frame grammar the kernels run (xrpl-coa-prototype_amd/csrc/coa_wire_parse.h)
-against the host decoder coa_wire.cpp, by a stand-alone program
-(tests/sanitize/wire_parse_driver.cpp) built with -fsanitize=address,undefined
-and run as a child process: the committed fuzz corpus, every strict prefix of
-its frames under 1 KiB, 20,000 seeded mutations and the constructed cases of
-tests/wire_dev_cases.py -- kind, lengths and every output byte equal, each
-frame in an exactly sized heap block.
+The library's one frame grammar (xrpl-coa-prototype_amd/csrc/coa_wire_parse.h)
+against the independent container-based model tests/sanitize/wire_model.h, by a
+stand-alone program (tests/sanitize/wire_parse_driver.cpp) built with
+-fsanitize=address,undefined and run as a child process.  Compared with the
+model, each way: the header's functions taken the way the kernels' lanes take
+them, and the host entries of coa_wire.cpp, the sequential driver of the same
+header.  Over the committed fuzz corpus, every strict prefix of its frames
+under 1 KiB, 20,000 seeded mutations, the constructed cases of
+tests/wire_dev_cases.py and one oversized header frame the program makes
+itself (300,000 payload entries: the host's set order is not quadratic) --
+kind, lengths and every output byte equal, each frame in an exactly sized heap
+block.
 
 And the new entries' return codes before any device work (n = 0, null arrays,
 no GPU) and the workspace size."""
@@ -31,7 +36,8 @@ MUTATIONS = 20_000
 def test_grammar_header_matches_host_decoder_under_sanitizers(tmp_path):
     exe = str(tmp_path / "wire_parse_driver")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", CSRC, SRC, os.path.join(CSRC, "coa_wire.cpp"), "-o", exe], check=True)
+                    "-I", CSRC, "-I", os.path.join(ROOT, "include"), SRC, os.path.join(CSRC, "coa_wire.cpp"), "-o", exe],
+                   check=True)
     constructed = cases.all_constructed()
     case_file = tmp_path / "cases.bin"
     with open(case_file, "wb") as f:
@@ -41,7 +47,7 @@ def test_grammar_header_matches_host_decoder_under_sanitizers(tmp_path):
     print(r.stdout, r.stderr)
     assert r.returncode == 0, r.stdout + r.stderr
     corpus = [open(os.path.join(CORPUS, n), "rb").read() for n in sorted(os.listdir(CORPUS)) if n.endswith(".bin")]
-    frames = len(corpus) + sum(len(f) for f in corpus if len(f) < 1024) + MUTATIONS + len(constructed)
+    frames = len(corpus) + sum(len(f) for f in corpus if len(f) < 1024) + MUTATIONS + len(constructed) + 1  # + the oversized frame
     lines = r.stdout.strip().splitlines()
     assert lines[-1] == f"ok {frames} frames"
     counts = dict(zip(lines[-2].split()[0::2], map(int, lines[-2].split()[1::2])))

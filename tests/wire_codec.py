@@ -2,7 +2,9 @@
 ENCODER for the primary's messages, written from the serde derives of the
 reference (primary/src/messages.rs:13-21,105-112,168-172,
 primary/src/primary.rs:33-38, crypto/src/lib.rs:94-112,177-182) -- used to
-feed the native decoder (coa_wire.cpp) frames it did not produce itself."""
+feed the native decoders (coa_wire.cpp on the host and coa_wire_dev.hip on the
+device, both drivers of the one grammar coa_wire_parse.h) frames they did not
+produce themselves."""
 import base64
 import struct
 

@@ -126,6 +126,7 @@ def malformed_keys():
         "too much padding": W.raw_key(base64.b64encode(k32) + b"=="),
         "not UTF-8": W.raw_key(b"\xff" * 44),
         "length prefix beyond the frame": b"\xff" * 8 + b"AAAA",
+        "one byte short": W.raw_key(base64.b64encode(k32[:31])),  # 44 characters, as a canonical key has
     }
 
 

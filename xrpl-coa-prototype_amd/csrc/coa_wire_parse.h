@@ -1,11 +1,40 @@
 // The grammar of a bincode PrimaryMessage frame, written once: the field walk,
 // the bounds rules, the UTF-8 and base64 rules of a PublicKey string, the error
 // codes' precedence (the first error in wire order decides) and the order of
-// 32-byte keys.  csrc/coa_wire.cpp is the host decoder these rules are pinned
-// against (tests/sanitize/wire_parse_driver.cpp compares the two frame by
-// frame); csrc/coa_wire_dev.hip runs them on the device and holds no second
-// copy.  Plain C++ and also compiled for the device (COA_WP_FN, in
+// 32-byte keys.  The library holds no second copy: csrc/coa_wire.cpp drives
+// these functions one frame after the other on the host, csrc/coa_wire_dev.hip
+// runs them across a wave's lanes on the device.  What they are pinned against
+// is outside the library: the container-based model tests/sanitize/
+// wire_model.h, which tests/sanitize/wire_parse_driver.cpp compares with both
+// frame by frame.  Plain C++ and also compiled for the device (COA_WP_FN, in
 // the way of coa_job_bits.h): no containers, no allocation, no HIP types.
+//
+// Format: bincode 1.3 `deserialize` (legacy options: little-endian, fixed-
+// width integers, u64 length prefixes, trailing bytes allowed) of
+//   PrimaryMessage = u32 variant: 0 Header, 1 Vote, 2 Certificate,
+//                    3 CertificatesRequest(Vec<Digest>, PublicKey)
+//   Header      author PublicKey | round u64 | payload BTreeMap<Digest, u32>
+//               | parents BTreeSet<Digest> | id Digest | signature
+//   Vote        id | round u64 | origin PublicKey | author PublicKey | signature
+//   Certificate header | votes Vec<(PublicKey, Signature)>
+//   Digest      32 raw bytes;  Signature  part1 32 | part2 32
+//   PublicKey   serde string (u64 length | UTF-8) holding base64 of the key
+//               (crypto/src/lib.rs:94-112); decode_base64 keeps the first 32
+//               decoded bytes (:72-78)
+// (primary/src/messages.rs:13-21,105-112,168-172).  BTreeMap/BTreeSet
+// deserialisation keeps the last value of a repeated key and iterates in key
+// order, and Header::digest hashes that iteration (messages.rs:70-84), so the
+// digest input a decoder emits is author | round LE | (digest | wid LE)* sorted
+// | parents* sorted -- the bytes the reference hashes, not the wire bytes.
+//
+// Errors are per frame (the reference drops a frame whose decode fails).
+// Where the reference would PANIC rather than error -- a base64 key that
+// decodes to fewer than 32 bytes hits `bytes[..32]` at crypto/src/lib.rs:74
+// -- these rules report COA_WIRE_EKEY instead.  base64 0.13 itself is not
+// available here: canonical padded keys (what every node emits) are decoded
+// exactly; for non-canonical forms this follows base64 0.13's documented
+// STANDARD rules (padding optional, no bytes after padding, zero trailing
+// bits) -- parity unpinned there.
 //
 // Every function reads the frame p[0, n) through byte loads only (fields sit
 // at arbitrary offsets: key strings are 43, 44, 64 ... characters long) and
@@ -20,8 +49,10 @@
 // Always inlined on the device: a kernel that has staged its frame in LDS
 // hands these functions an LDS pointer, and only inlined code lets the compiler
 // keep the address space (LDS reads that do not queue behind global stores).
+// Spelled out (it is what __forceinline__ expands to) so that a host-only
+// translation unit compiled as HIP needs no hip_runtime.h before this header.
 #if defined(__HIPCC__)
-#define COA_WP_FN __host__ __device__ __forceinline__
+#define COA_WP_FN __host__ __device__ inline __attribute__((always_inline))
 #else
 #define COA_WP_FN inline
 #endif
@@ -70,7 +101,8 @@ COA_WP_FN int coa_wp_b64_val(uint8_t c) {
   return -1;
 }
 
-// serde String: the bytes must be UTF-8 (structure check, as coa_wire.cpp)
+// serde String: the bytes must be UTF-8 (structure check; a key is ASCII
+// base64 anyway, so any non-ASCII byte fails one way or the other)
 COA_WP_FN bool coa_wp_utf8_valid(const uint8_t* s, size_t n) {
   size_t i = 0;
   while (i < n) {
@@ -89,7 +121,7 @@ COA_WP_FN bool coa_wp_utf8_valid(const uint8_t* s, size_t n) {
   return true;
 }
 
-// A PublicKey at *pos: u64 length | string.  The checks in the host's order:
+// A PublicKey at *pos: u64 length | string.  The checks in this order:
 // the length against the frame's end (COA_WIRE_ETRUNC), UTF-8
 // (COA_WIRE_EFORMAT), base64 STANDARD with optional padding, nothing after
 // the padding and zero trailing bits, of at least 32 bytes (COA_WIRE_EKEY).
@@ -132,7 +164,8 @@ COA_WP_FN int coa_wp_key(const uint8_t* p, size_t n, size_t* pos, uint8_t* out) 
   return COA_OK;
 }
 
-// What the walk finds: positions of the fields, none of them decoded.
+// What the walk finds: positions of the fields, none of them decoded (the
+// walk can hand out the keys it has to check anyway: coa_wp_walk).
 struct CoaWpFrame {
   int32_t kind;                      // COA_MSG_* so far, or the first error
   // Header (and Certificate.header)
@@ -147,12 +180,13 @@ struct CoaWpFrame {
   uint64_t v_round;
 };
 
-// Header at *pos (coa_wire.cpp's read_header, its up-front count checks
-// included); COA_OK or the first error.
-COA_WP_FN int coa_wp_header(const uint8_t* p, size_t n, size_t* pos, CoaWpFrame* f) {
+// Header at *pos; each count is checked against the bytes left before its
+// entries are stepped over.  COA_OK or the first error.  author: null, or 32
+// bytes for the decoded key.
+COA_WP_FN int coa_wp_header(const uint8_t* p, size_t n, size_t* pos, CoaWpFrame* f, uint8_t* author = nullptr) {
   size_t i = *pos;
   f->author = i;
-  const int rc = coa_wp_key(p, n, &i, nullptr);
+  const int rc = coa_wp_key(p, n, &i, author);
   if (rc != COA_OK) return rc;
   if (n - i < 16) return COA_WIRE_ETRUNC;
   f->round = coa_wp_u64(p + i);
@@ -177,7 +211,11 @@ COA_WP_FN int coa_wp_header(const uint8_t* p, size_t n, size_t* pos, CoaWpFrame*
 // The frame up to, and without, a certificate's vote list: f->kind is the
 // variant when everything walked is well formed (a Certificate's votes are
 // still to be checked: coa_wp_votes or coa_wp_vote per vote), else the error.
-COA_WP_FN int coa_wp_walk(const uint8_t* p, size_t n, CoaWpFrame* f) {
+// key0, key1: null, or 32 bytes each for the keys the walk checks on its way,
+// so that a sequential caller need not read them twice -- a Header's or
+// Certificate's author in key0, a Vote's origin in key0 and author in key1;
+// their content is unspecified unless the walk returns the variant.
+COA_WP_FN int coa_wp_walk(const uint8_t* p, size_t n, CoaWpFrame* f, uint8_t* key0 = nullptr, uint8_t* key1 = nullptr) {
   f->np = f->nq = f->nv = 0;
   if (n < 4) return f->kind = COA_WIRE_ETRUNC;
   const uint32_t variant = coa_wp_u32(p);
@@ -185,7 +223,7 @@ COA_WP_FN int coa_wp_walk(const uint8_t* p, size_t n, CoaWpFrame* f) {
   int rc = COA_OK;
   switch (variant) {
     case COA_MSG_HEADER:
-      rc = coa_wp_header(p, n, &i, f);
+      rc = coa_wp_header(p, n, &i, f, key0);
       break;
     case COA_MSG_VOTE:
       if (n - i < 40) return f->kind = COA_WIRE_ETRUNC;
@@ -193,14 +231,14 @@ COA_WP_FN int coa_wp_walk(const uint8_t* p, size_t n, CoaWpFrame* f) {
       f->v_round = coa_wp_u64(p + i + 32);
       i += 40;
       f->v_origin = i;
-      if ((rc = coa_wp_key(p, n, &i, nullptr)) != COA_OK) break;
+      if ((rc = coa_wp_key(p, n, &i, key0)) != COA_OK) break;
       f->v_author = i;
-      if ((rc = coa_wp_key(p, n, &i, nullptr)) != COA_OK) break;
+      if ((rc = coa_wp_key(p, n, &i, key1)) != COA_OK) break;
       f->v_sig = i;
       if (n - i < 64) rc = COA_WIRE_ETRUNC;
       break;
     case COA_MSG_CERTIFICATE:
-      if ((rc = coa_wp_header(p, n, &i, f)) != COA_OK) break;
+      if ((rc = coa_wp_header(p, n, &i, f, key0)) != COA_OK) break;
       if (n - i < 8) {
         rc = COA_WIRE_ETRUNC;
         break;
@@ -269,9 +307,9 @@ COA_WP_FN uint64_t coa_wp_error_word(uint64_t index, int rc) {
 }
 COA_WP_FN int coa_wp_error_code(uint64_t word) { return word == COA_WP_NO_ERROR ? COA_OK : -(int)(word & 0xff); }
 
-// A frame the host decoder accepts but whose sets are beyond what the device
-// sorts: COA_WIRE_ECAPACITY (the caller decodes it on the host).  Every host
-// error has been decided before this is asked.
+// A well-formed frame whose sets are beyond what the device sorts:
+// COA_WIRE_ECAPACITY (the caller decodes it on the host, which has no cap).
+// Every error of the grammar has been decided before this is asked.
 COA_WP_FN int32_t coa_wp_capacity(int32_t kind, uint64_t np, uint64_t nq) {
   if ((kind == COA_MSG_HEADER || kind == COA_MSG_CERTIFICATE) &&
       (np > COA_WIRE_DEV_MAX_ENTRIES || nq > COA_WIRE_DEV_MAX_ENTRIES))
