@@ -5,7 +5,7 @@ blocks assembled into `.subsection 1` are left out): the outermost loop of the
 kernel is the digit loop, the loop nested in it the three-pass doubling loop,
 so one digit issues  body(outer) - body(inner) + 3 * body(inner)  instructions
 (the body includes the conversion that every digit but the last ends with).
-k_verify_main_sums has one digit loop per role (the outermost loops with a
+k_verify_main_sums and k_verify_main_sums29 have one digit loop per role (the outermost loops with a
 barrier in them): the consumer's is the one with the doubling loop nested in
 it, the producer's the one without.
 Also prints the straight-line hot-path count of both k_pre_halve<3, *>
@@ -20,7 +20,8 @@ compared by diffing two small files.
 For both k_pre_halve<3, *> instances it also lists the hot-path loops with
 their body counts (the squaring runs of the (p-5)/8 chains are the loops
 without memory instructions).  -D NAME=VALUE is passed to the compiler
-(-D COA_PRE_POW29=0: the radix-2^32 decompression).
+(-D COA_PRE_POW29=0: the radix-2^32 decompression; -D COA_SUMS_FE29=0: no
+k_verify_main_sums29).
 
 usage: python tools/digit_count.py [--json FILE] [-D NAME=VALUE ...] [coa_halved.s]
        (without a .s argument the file is compiled here with build.py's flags)"""
@@ -39,6 +40,7 @@ sys.path.insert(0, os.path.join(ROOT, "xrpl-coa-prototype_amd"))
 
 MAIN = "_Z13k_verify_mainILi1ELb1EEv"
 SUMS = "_Z18k_verify_main_sumsILi0ELb0EEv"
+SUMS29 = "_Z20k_verify_main_sums29ILi0ELb0EEv"  # the limb-form accumulator (COA_SUMS_FE29)
 PRE = "_Z11k_pre_halveILi3E"
 WATCH = ("v_mad_u64_u32", "v_addc_co_u32", "v_mov_b32", "v_cndmask_b32", "s_nop")
 KEYS = ["all"] + list(WATCH)
@@ -123,9 +125,9 @@ def digit(text):
     return {k: o[k] + 2 * i[k] for k in KEYS}, {k: i[k] for k in KEYS}
 
 
-def sums_digit(text):
-    """(consumer per digit, its doubling pass, producer per digit) of k_verify_main_sums."""
-    lines = function_lines(text, SUMS)
+def sums_digit(text, prefix=SUMS):
+    """(consumer per digit, its doubling pass, producer per digit) of k_verify_main_sums / _sums29."""
+    lines = function_lines(text, prefix)
     ls = loops(lines)
     top = [r for r in ls if not any(o != r and o[0] <= r[0] and r[1] <= o[1] for o in ls)]
     # a role's digit loop ends each iteration with the barrier; the consumer's
@@ -198,6 +200,13 @@ def main():
         print("  one doubling pass:", fmt(sd[1]))
         print("k_verify_main_sums<0,false> producer per digit:", fmt(sd[2]))
         report[sums_k].update(consumer_per_digit=sd[0], doubling_pass=sd[1], producer_per_digit=sd[2])
+    sums29_k = next((k for k in meta if k.startswith(SUMS29)), None)
+    sd = sums_digit(text, SUMS29) if sums29_k else None
+    if sd:
+        print("k_verify_main_sums29<0,false> consumer per digit:", fmt(sd[0]))
+        print("  one doubling pass:", fmt(sd[1]))
+        print("k_verify_main_sums29<0,false> producer per digit:", fmt(sd[2]))
+        report[sums29_k].update(consumer_per_digit=sd[0], doubling_pass=sd[1], producer_per_digit=sd[2])
     for name in meta:
         if name.startswith(PRE):
             lines = function_lines(text, name + ":")

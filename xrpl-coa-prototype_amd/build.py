@@ -25,7 +25,7 @@ HEADERS = ["coa_fe.h", "coa_sc.h", "coa_ge.h", "coa_sha512.h", "coa_smul.h", "co
            "coa_committee.h", "coa_msm.h", "coa_fe_wave.h", "coa_ge_rows.h", "coa_halve.h", "coa_keycache.h",
            "coa_latency.h", "coa_queue.h", "coa_rcmp.h", "coa_lehmer.h", "coa_ge_sums.h", "coa_protocol.h",
            "coa_protocol_dev.h", "coa_prot_scan.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
-           "coa_hostpool.h", "coa_job_bits.h", "coa_cert_scratch.h", "coa_lat_job.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge_dec29.h",
+           "coa_hostpool.h", "coa_job_bits.h", "coa_cert_scratch.h", "coa_lat_job.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge_dec29.h", "coa_ge29.h",
            "coa_batch_dev.h", "coa_resolve.h", "coa_resolve_ws.h", "coa_wire_parse.h", "coa_wire_dev.h"]
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffunction-sections", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 
@@ -77,17 +77,18 @@ def build(verbose=False):
 
 
 ARITH_HEADERS = ["coa_fe.h", "coa_fe_wave.h", "coa_sc.h", "coa_halve.h", "coa_lehmer.h", "coa_ge.h", "coa_smul.h",
-                 "coa_halved.h", "coa_ge_sums.h", "coa_ge_rows.h", "coa_sums_tail.h", "coa_fe_pow29.h"]
+                 "coa_halved.h", "coa_ge_sums.h", "coa_ge_rows.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge29.h"]
 # test-only device libraries around the arithmetic headers: (sources under tests/arith/, library under lib/)
 ARITH_LIBS = [(["arith_check.hip", "pow29_check.hip"], "libcoa_arithcheck.so"),
               (["alias_check.hip"], "libcoa_aliascheck.so"), (["sums_check.hip"], "libcoa_sumscheck.so"),
-              (["tail_check.hip"], "libcoa_tailcheck.so")]
+              (["tail_check.hip"], "libcoa_tailcheck.so"), (["ge29_check.hip"], "libcoa_ge29check.so")]
 ARITH_SRC = os.path.join(ROOT, "tests", "arith", ARITH_LIBS[0][0][0])
 ARITH_LIB = os.path.join(LIBDIR, ARITH_LIBS[0][1])
 
 
 def _build_arithcheck():
-    """lib/libcoa_arithcheck.so, libcoa_aliascheck.so, libcoa_sumscheck.so and libcoa_tailcheck.so: the test-only
+    """lib/libcoa_arithcheck.so, libcoa_aliascheck.so, libcoa_sumscheck.so, libcoa_tailcheck.so and
+    libcoa_ge29check.so: the test-only
     kernels of tests/arith/*.hip around the arithmetic headers (no C-ABI
     entry).  Each source is compiled twice with the engine's COMMON flags, as
     is and with -DCOA_RARE_INLINE, so both assembled forms of the rare carry

@@ -50,6 +50,15 @@
 #include "coa_ge_dec29.h"
 #endif
 #include "coa_ge_sums.h"
+// k_verify_main_sums' accumulator: 1 = k_verify_main_sums29 (coa_ge29.h, the
+// consumer's point on 29-bit limbs) beside the radix-2^32 kernel, chosen per
+// call by COA_SUMS_FE29 (environment); 0 = the radix-2^32 kernel alone.
+#ifndef COA_SUMS_FE29
+#define COA_SUMS_FE29 1
+#endif
+#if COA_SUMS_FE29
+#include "coa_ge29.h"
+#endif
 #include "coa_halve.h"
 #include "coa_halved_dev.h"
 #include "coa_main_pick.h"
@@ -715,6 +724,147 @@ __global__ void __launch_bounds__(512) k_verify_main_sums(const uint32_t* __rest
   if (live) verdicts[i] = verdict;
 }
 
+#if COA_SUMS_FE29
+// k_verify_main_sums with the consumers' accumulator on nine carry-free 29-bit
+// limbs (coa_ge29.h): the doublings and the addition of a digit issue a tenth
+// fewer instructions, and no carry chain.  Roles, slots, H, the digit cap, the
+// barriers (1 + H per role, none under a per-lane condition) and the handling
+// of dead and rejected lanes are k_verify_main_sums', which stays as it is
+// beside this kernel (COA_SUMS_FE29=0 in the environment picks it per call).
+// The producers keep the radix-2^32 field -- their table entries are stored in
+// it -- and convert the four fields of S to limbs, so a slot holds 36 dwords
+// per item; the row prologue's result is converted once on the way in, and the
+// accumulator once on the way out, where [e]B and the identity test run once
+// per item on coa_ge.h.
+template <int PRIO, bool SWAP>
+__global__ void __launch_bounds__(512) k_verify_main_sums29(const uint32_t* __restrict__ rec,
+                                                            const uint8_t* __restrict__ flags, uint32_t n,
+                                                            uint8_t* __restrict__ verdicts,
+                                                            const uint32_t* __restrict__ scr,
+                                                            const uint32_t* __restrict__ ebp, int tail_max) {
+  __shared__ uint32_t s_lds[2][36][256];  // 72 KiB; the H exchange borrows s_lds[0][0][0..7] first
+  const uint32_t slot_item = threadIdx.x & 255u;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, in an SGPR
+  const bool producer = SWAP ? wave < 4 : wave >= 4;
+  const uint32_t i = blockIdx.x * 256u + slot_item;
+  const bool live = i < n;
+  const uint32_t ii = live ? i : 0u;  // every load below is in bounds
+  const uint32_t* myrec = rec + (uint64_t)ii * 32;
+  const uint16_t fl = reinterpret_cast<const uint16_t*>(flags)[ii];
+  const uint32_t meta0 = myrec[24];
+  const bool ok = live && fl == 0x0101u;
+  const uint32_t meta = ok ? meta0 : 0u;
+  const int hi = (int)(meta & 0xffu);
+  const int hw = wave_max(hi);
+  const int tw = __popcll(__builtin_amdgcn_ballot_w64(hi > COA_SUMS_CAP));
+  if ((threadIdx.x & 63u) == 0) s_lds[0][0][wave] = (uint32_t)(hw | tw << 8);
+  __syncthreads();
+  int Hwg = 0, tails = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+    const uint32_t v = s_lds[0][0][w];
+    Hwg = max(Hwg, (int)(v & 0xffu));
+    tails = max(tails, (int)(v >> 8));
+  }
+  Hwg = __builtin_amdgcn_readfirstlane(Hwg);
+  tails = __builtin_amdgcn_readfirstlane(tails);
+  __syncthreads();  // the exchange words are read before the first sum overwrites them
+  const int H = tails <= tail_max ? min(Hwg, COA_SUMS_CAP) : Hwg;
+  if constexpr (PRIO != 0) {
+    if (producer == (PRIO == 2)) __builtin_amdgcn_s_setprio(2);
+  }
+  if (producer) {
+    uint32_t cw[8], dw[8];  // the digit words
+    load8_u4(cw, myrec);
+    load8_u4(dw, myrec + 8);
+    if (!ok) {  // zero digits: such a lane adds the identity at every position
+#pragma unroll
+      for (int j = 0; j < 8; j++) cw[j] = dw[j] = 0x88888888u;
+    }
+    const bool dneg = (meta >> 31) != 0;
+    auto produce = [&](int pos) {  // S_pos, in limbs, into slot pos & 1
+      const int sh = 4 * (pos & 7);
+      const int dc = (int)((cw[pos >> 3] >> sh) & 15u) - 8;
+      const int dd = (int)((dw[pos >> 3] >> sh) & 15u) - 8;
+      const int dr = dneg ? -dd : dd;
+      ge_cached qa, qr, c;
+      tab2_load(qa, scr, i, 0, dc);
+      tab2_load(qr, scr, i, 1, dr);
+      ge_p1p1 u;
+      ge_p3 s3;
+      ge_add_cc_il(u, qa, qr, (dc < 0) != (dr < 0));
+      ge_p1p1_to_p3_il(s3, u);
+      ge_p3_to_cached(c, s3);
+      const fe* f[4] = {&c.YplusX, &c.YminusX, &c.Z, &c.T2d};
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        fe29 l;
+        fe29_from_fe(l, *f[q]);
+#pragma unroll
+        for (int k = 0; k < 9; k++) s_lds[pos & 1][9 * q + k][slot_item] = l.v[k];
+      }
+    };
+    if (H > 0) produce(H - 1);
+    __syncthreads();
+#pragma unroll 1
+    for (int pos = H - 1; pos >= 0; pos--) {
+      if (pos > 0) produce(pos - 1);
+      __syncthreads();
+    }
+    return;  // after the last barrier
+  }
+  ge_p3 acc32;
+  ge_p3_identity(acc32);
+  // tail lanes start from 16 * (their digits at positions >= H), computed on
+  // the rows in the radix-2^32 field; H < Hwg is uniform over the workgroup
+  if (H < Hwg) sums_tail::prologue(acc32, hi > H, i, meta, rec, scr, H);
+  ge29_p3 acc3;
+  ge29_p2 acc2;
+  ge29_p1p1 t;
+  ge29_p3_from(acc3, acc32);
+  ge29_p1p1_identity(t);  // what the tail converts when H == 0
+  __syncthreads();
+#pragma unroll 1
+  for (int pos = H - 1; pos >= 0; pos--) {
+    ge29_cached sq;
+    fe29* f[4] = {&sq.YplusX, &sq.YminusX, &sq.Z, &sq.T2d};
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+      for (int k = 0; k < 9; k++) f[q]->v[k] = s_lds[pos & 1][9 * q + k][slot_item];
+    if (pos != H - 1) {
+#pragma unroll 1
+      for (int k = 0; k < 3; k++) {
+        ge29_p2_dbl(t, acc2);
+        ge29_p1p1_to_p2(acc2, t);
+      }
+      ge29_p2_dbl(t, acc2);
+      ge29_p1p1_to_p3(acc3, t);
+    }
+    ge29_add(t, acc3, sq);
+    if (pos != 0) ge29_p1p1_to_p2(acc2, t);
+    __syncthreads();
+  }
+  uint8_t verdict = 1;
+  if (ok) {
+    ge29_p1p1_to_p3(acc3, t);
+    ge29_p3_to(acc32, acc3);
+    // + [e]B, computed by the halving role
+    ge_cached eb;
+    fe* fb[4] = {&eb.YplusX, &eb.YminusX, &eb.Z, &eb.T2d};
+#pragma unroll
+    for (int q = 0; q < 4; q++) load8_u4(fb[q]->v, ebp + (uint64_t)i * 32 + 8 * q);
+    ge_p1p1 u;
+    ge_add(u, acc32, eb);
+    ge_p1p1_to_p3(acc32, u);
+    ge_p2 q2;
+    ge_p3_to_p2(q2, acc32);
+    verdict = ge_p2_is_identity(q2) ? 0 : 1;
+  }
+  if (live) verdicts[i] = verdict;
+}
+#endif
+
 template <int WAVES>
 __global__ void __launch_bounds__(256, WAVES) k_verify_halved(const uint8_t* __restrict__ pks,
                                                           const uint8_t* __restrict__ sigs,
@@ -865,6 +1015,10 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   // COA_SUMS_TAIL_MAX, read per call (A/B and tests): coa_sums_tail.h
   const char* tm = getenv("COA_SUMS_TAIL_MAX");
   const int tail_max = tm ? atoi(tm) : COA_SUMS_TAIL_MAX;
+#if COA_SUMS_FE29
+  // COA_SUMS_FE29=0, read per call (A/B and tests): the radix-2^32 accumulator
+  const bool sums_fe29 = coa_env_switch(getenv("COA_SUMS_FE29")) != 0;
+#endif
   // phase 1 stores table 1 in the form the main kernel launched below reads
   if (kernel == COA_MAIN_SUMS)
     hipLaunchKernelGGL((k_pre_halve<3, true>), dim3(3 * blocks), dim3(pre_b), 0, s, pks, sigs, msgs, msg_len, aligned,
@@ -877,6 +1031,13 @@ hipError_t coa_launch_verify_split(const uint8_t* pks, const uint8_t* sigs, cons
   const dim3 main_grid((n + main_b - 1) / main_b);
   switch (kernel) {
     case COA_MAIN_SUMS:
+#if COA_SUMS_FE29
+      if (sums_fe29) {
+        hipLaunchKernelGGL((k_verify_main_sums29<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512),
+                           0, s, rec, flags, n, verdicts, scratch, ebp, tail_max);
+        break;
+      }
+#endif
       hipLaunchKernelGGL((k_verify_main_sums<COA_SUMS_PRIO, COA_SUMS_SWAP != 0>), dim3((n + 255) / 256), dim3(512), 0,
                          s, rec, flags, n, verdicts, scratch, ebp, tail_max);
       break;
