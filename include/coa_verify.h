@@ -490,8 +490,9 @@ int coa_wire_decode_headers(const uint8_t* frames, const uint64_t* frame_offsets
  * COA_WIRE_E*, or COA_WIRE_ECAPACITY -- and item i is an empty placeholder:
  * zeroed id, keys, signature, round and payload count, no header bytes and no
  * votes (offsets[i+1] == offsets[i]).  The caller reads d_kinds before it
- * trusts item i.  Sorting frames into per-kind batches is the caller's: it
- * needs a frame's first four bytes only and no decode.
+ * trusts item i.  Sorting frames into per-kind batches is the caller's (it
+ * needs a frame's first four bytes only and no decode), or the mixed mode's
+ * below, which partitions one batch by kind on the device.
  *   COA_WIRE_ECAPACITY  a Header or Certificate frame the host decoder
  *       accepts whose wire count of payload entries or of parents exceeds
  *       COA_WIRE_DEV_MAX_ENTRIES (every host error takes precedence); the
@@ -551,6 +552,67 @@ int coa_wire_header_verdict_many(const uint8_t* frames, const uint64_t* frame_of
                                  uint32_t* verdicts_out);
 int coa_wire_vote_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, int32_t* kinds_out,
                                uint32_t* verdicts_out);
+
+/* ------------------------------- mixed frame batches on the device (f4)
+ * One batch in which headers, votes, certificates and certificate requests
+ * arrive interleaved, as PrimaryReceiverHandler::dispatch receives them:
+ * a stable partition of the batch by kind on the device, so the caller neither
+ * sorts the frames nor pays a placeholder's signature job.
+ *
+ * coa_wire_decode_mixed_device: frames, offsets, frame_bytes and the range
+ * rule as the decoders above (no frame byte outside its checked range is
+ * read).  The scan is theirs; the prefix sums then run over six quantities
+ * (headers: frames, header bytes; votes: frames; certificates: frames, header
+ * bytes, votes) in the same three launches.  d_slots[i] is the rank of frame
+ * i among the frames of its kind, in frame order, where d_kinds[i] is
+ * COA_MSG_HEADER, COA_MSG_VOTE or COA_MSG_CERTIFICATE, and COA_WIRE_NO_SLOT
+ * for every other frame (a certificate request, a negative COA_WIRE_E*,
+ * COA_WIRE_ECAPACITY).  Frame i of kind k is decoded into item d_slots[i] of
+ * kind k's array set: the d_h_* arrays are coa_wire_decode_headers_device's,
+ * the d_v_* arrays coa_wire_decode_votes_device's and the d_c_* arrays
+ * coa_wire_decode_certificates_device's, each at the capacity that call
+ * states (n per-item entries, n + 1 offsets, frame_bytes + 16 header bytes,
+ * COA_WIRE_VOTES_BOUND(frame_bytes) vote rows).  With n_k frames of kind k,
+ * items [0, n_k) of its set and its offsets on [0, n_k] (offsets[0] = 0) are
+ * exactly what the single-kind decoder gives for the batch's frames of that
+ * kind alone, in order; there are no placeholders, and nothing at or above
+ * n_k (offsets: above n_k) is written.
+ *   d_totals: eight words -- headers, header bytes of headers, votes,
+ *       certificates, header bytes of certificates, votes of certificates,
+ *       frames without a slot, 0.
+ * `workspace`: at least coa_wire_mixed_workspace_bytes(n, frame_bytes) bytes
+ * of device memory -- the call then only enqueues (no host synchronisation, no
+ * copy, no allocation) -- or NULL: engine-owned, and the call waits for its
+ * stream.  n = 0 returns COA_OK; a null required array or an n or frame_bytes
+ * too large for one call COA_EINVAL; no device COA_ENODEVICE. */
+#define COA_WIRE_NO_SLOT 0xFFFFFFFFu
+size_t coa_wire_mixed_workspace_bytes(size_t n, size_t frame_bytes);
+int coa_wire_decode_mixed_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                                 size_t frame_bytes, uint8_t* d_h_header_data, uint64_t* d_h_header_offsets,
+                                 uint8_t* d_h_ids, uint8_t* d_h_authors, uint8_t* d_h_sigs,
+                                 uint32_t* d_h_payload_counts, uint64_t* d_h_rounds, uint8_t* d_v_ids,
+                                 uint64_t* d_v_rounds, uint8_t* d_v_origins, uint8_t* d_v_authors, uint8_t* d_v_sigs,
+                                 uint8_t* d_c_header_data, uint64_t* d_c_header_offsets, uint8_t* d_c_ids,
+                                 uint8_t* d_c_origins, uint8_t* d_c_header_sigs, uint64_t* d_c_rounds,
+                                 uint8_t* d_c_vote_pks, uint8_t* d_c_vote_sigs, uint64_t* d_c_vote_offsets,
+                                 uint32_t* d_c_payload_counts, int32_t* d_kinds, uint32_t* d_slots,
+                                 uint64_t* d_totals, void* workspace, void* stream);
+/* Mixed frames to verdicts, host pointers: one H2D of the frames and their
+ * offsets, the mixed decode, one 64-byte read-back of d_totals (the verdict
+ * calls take their counts, the certificate call its vote count, as host
+ * arguments), then on the same stream and over the compacted arrays at their
+ * own counts coa_header_verdict_many_device, coa_vote_verdict_many_device and
+ * coa_certificate_verdict_many_device + coa_certificate_votes_resolve_device
+ * (a kind with no frame launches nothing), the scatter of the words back to
+ * frame order and one D2H of kinds and words, on one context.  kinds_out[i] is
+ * the scan's answer; verdicts_out[i] is frame i's COA_DAG_* word -- for each
+ * kind exactly what the single-kind call above answers on the batch's frames
+ * of that kind alone, in order, with the same rng_seed -- and
+ * COA_DAG_NO_MESSAGE for a frame without a slot; never COA_DAG_VOTES_OPEN.
+ * Arguments are accepted and rejected as by the calls above; a generation
+ * without a protocol table gives COA_EINVAL. */
+int coa_wire_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, uint64_t rng_seed,
+                          int32_t* kinds_out, uint32_t* verdicts_out);
 
 /* --------------------------------------------------------------- signing
  * RFC 8032 signing == crypto::Signature::new (crypto/src/lib.rs:185-191) /
@@ -639,6 +701,16 @@ int coa_cpu_vote_verdict_many(const uint8_t* ids, const uint64_t* rounds, const 
                               const uint8_t* authors, const uint8_t* sigs, size_t n, const uint8_t* committee_pks,
                               const uint32_t* stakes, const uint32_t* worker_ids, const uint64_t* worker_offsets,
                               size_t n_authorities, uint32_t* verdicts_out, int nthreads);
+/* coa_wire_verdict_many on the CPU path: coa_wire_scan, the partition by kind
+ * on the host, the three host decoders, the three calls above and the scatter
+ * back to frame order.  kinds_out and verdicts_out as coa_wire_verdict_many,
+ * but for one case: the host decoder has no entry cap, so a frame the device
+ * reports as COA_WIRE_ECAPACITY is answered here as its real kind with a real
+ * word. */
+int coa_cpu_wire_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, uint64_t rng_seed,
+                              const uint8_t* committee_pks, const uint32_t* stakes, const uint32_t* worker_ids,
+                              const uint64_t* worker_offsets, size_t n_authorities, int32_t* kinds_out,
+                              uint32_t* verdicts_out, int nthreads);
 
 /* ------------------------------------------------ aggregation queue (f1)
  * Pre-verification stage for Core::run (primary/src/core.rs:349-389), which

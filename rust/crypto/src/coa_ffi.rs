@@ -263,6 +263,21 @@ extern "C" {
                                         verdicts_out: *mut u32) -> c_int;
     pub fn coa_wire_vote_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, kinds_out: *mut i32,
                                       verdicts_out: *mut u32) -> c_int;
+    // mixed batches: the partition by kind on the device, one verdict word per frame
+    pub fn coa_wire_mixed_workspace_bytes(n: usize, frame_bytes: usize) -> usize;
+    pub fn coa_wire_decode_mixed_device(device: c_int, d_frames: *const u8, d_frame_offsets: *const u64, n: usize,
+                                        frame_bytes: usize, d_h_header_data: *mut u8, d_h_header_offsets: *mut u64,
+                                        d_h_ids: *mut u8, d_h_authors: *mut u8, d_h_sigs: *mut u8,
+                                        d_h_payload_counts: *mut u32, d_h_rounds: *mut u64, d_v_ids: *mut u8,
+                                        d_v_rounds: *mut u64, d_v_origins: *mut u8, d_v_authors: *mut u8,
+                                        d_v_sigs: *mut u8, d_c_header_data: *mut u8, d_c_header_offsets: *mut u64,
+                                        d_c_ids: *mut u8, d_c_origins: *mut u8, d_c_header_sigs: *mut u8,
+                                        d_c_rounds: *mut u64, d_c_vote_pks: *mut u8, d_c_vote_sigs: *mut u8,
+                                        d_c_vote_offsets: *mut u64, d_c_payload_counts: *mut u32, d_kinds: *mut i32,
+                                        d_slots: *mut u32, d_totals: *mut u64, workspace: *mut c_void,
+                                        stream: *mut c_void) -> c_int;
+    pub fn coa_wire_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, rng_seed: u64,
+                                 kinds_out: *mut i32, verdicts_out: *mut u32) -> c_int;
 
     // ----------------------------------------------------------- signing
     pub fn coa_ed25519_public_keys(seeds: *const u8, n: usize, pks_out: *mut u8) -> c_int;
@@ -323,6 +338,10 @@ extern "C" {
     pub fn coa_cpu_vote_verdict_many(ids: *const u8, rounds: *const u64, origins: *const u8, authors: *const u8,
                                      sigs: *const u8, n: usize, committee_pks: *const u8, stakes: *const u32,
                                      worker_ids: *const u32, worker_offsets: *const u64, n_authorities: usize,
+                                     verdicts_out: *mut u32, nthreads: c_int) -> c_int;
+    pub fn coa_cpu_wire_verdict_many(frames: *const u8, frame_offsets: *const u64, n: usize, rng_seed: u64,
+                                     committee_pks: *const u8, stakes: *const u32, worker_ids: *const u32,
+                                     worker_offsets: *const u64, n_authorities: usize, kinds_out: *mut i32,
                                      verdicts_out: *mut u32, nthreads: c_int) -> c_int;
 
     // ------------------------------------------------- aggregation queue (f1)

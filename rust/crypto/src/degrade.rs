@@ -182,3 +182,35 @@ pub fn cpu_certificate_bits(header_input: &[u8], id: &[u8], origin: &[u8], heade
     cpu_status(rc, "Certificate::verify");
     status[0]
 }
+
+/// `config::Committee` as the arrays `coa_committee_register_authorities` and
+/// the stateless `coa_cpu_*_verdict_many` calls take: authority i has key
+/// `keys[32 i ..]`, stake `stakes[i]` and the worker ids
+/// `worker_ids[worker_offsets[i] .. worker_offsets[i + 1])`.
+pub struct CommitteeArrays {
+    pub keys: Vec<u8>,
+    pub stakes: Vec<u32>,
+    pub worker_ids: Vec<u32>,
+    pub worker_offsets: Vec<u64>,
+}
+
+/// "dispatch, then verify" (primary/src/primary.rs:223-244, then
+/// primary/src/messages.rs:48-67, 131-142, 189-215) for a receive buffer of
+/// interleaved frames on the engine's CPU path: per frame its kind and its
+/// COA_DAG_* word, COA_DAG_NO_MESSAGE where the reference drops the frame.
+/// `frames` is the buffer, frame i its bytes `offsets[i] .. offsets[i + 1]`.
+pub fn cpu_wire_verdicts(frames: &[u8], offsets: &[u64], rng_seed: u64, committee: &CommitteeArrays) -> (Vec<i32>, Vec<u32>) {
+    let n = offsets.len().saturating_sub(1);
+    let na = committee.stakes.len();
+    assert!(committee.keys.len() == 32 * na && committee.worker_offsets.len() == na + 1);
+    let mut kinds = vec![0i32; n];
+    let mut words = vec![0xffu32; n];
+    let rc = unsafe {
+        ffi::coa_cpu_wire_verdict_many(frames.as_ptr(), offsets.as_ptr(), n, rng_seed, committee.keys.as_ptr(),
+                                       committee.stakes.as_ptr(), committee.worker_ids.as_ptr(),
+                                       committee.worker_offsets.as_ptr(), na, kinds.as_mut_ptr(), words.as_mut_ptr(),
+                                       CPU_THREADS)
+    };
+    cpu_status(rc, "PrimaryMessage frames (many)");
+    (kinds, words)
+}

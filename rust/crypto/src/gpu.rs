@@ -237,6 +237,35 @@ pub fn votes_verify_many(items: &[VoteItem]) -> Vec<Result<(), CryptoError>> {
     out.into_iter().map(|v| if v == 0 { Ok(()) } else { Err(CryptoError::new()) }).collect()
 }
 
+/// "dispatch, then verify" for a receive buffer in which headers, votes,
+/// certificates and certificate requests arrive interleaved
+/// (primary/src/primary.rs:223-244): ONE upload, the partition by kind and the
+/// decode on the device, `Header::verify`, `Vote::verify` and
+/// `Certificate::verify` over each kind's frames, and per frame its kind
+/// (COA_MSG_* or a negative COA_WIRE_E*) and its COA_DAG_* word in frame order;
+/// COA_DAG_NO_MESSAGE (255) for a certificate request and for a frame the
+/// reference drops.  `committee` is the registered committee: the engine's CPU
+/// path is stateless and takes it in the call when the engine has failed.
+pub fn wire_verdict_many(frames: &[&[u8]], rng_seed: u64, committee: &degrade::CommitteeArrays) -> (Vec<i32>, Vec<u32>) {
+    let n = frames.len();
+    let mut data = Vec::with_capacity(frames.iter().map(|f| f.len()).sum::<usize>() + 1);
+    let mut offsets = Vec::with_capacity(n + 1);
+    offsets.push(0u64);
+    for f in frames {
+        data.extend_from_slice(f);
+        offsets.push(data.len() as u64);
+    }
+    data.push(0); // never a dangling pointer for an all-empty window
+    let mut kinds = vec![0i32; n];
+    let mut words = vec![0xffu32; n];
+    if !engine_ok(unsafe {
+        ffi::coa_wire_verdict_many(data.as_ptr(), offsets.as_ptr(), n, rng_seed, kinds.as_mut_ptr(), words.as_mut_ptr())
+    }, "PrimaryMessage frames (many)") {
+        return degrade::cpu_wire_verdicts(&data, &offsets, rng_seed, committee);
+    }
+    (kinds, words)
+}
+
 /// Many certificates' vote batches in one launch: one verify_batch verdict
 /// per group (certificate), votes concatenated, group g = votes of
 /// certificate g over digests[g].

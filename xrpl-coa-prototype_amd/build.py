@@ -20,13 +20,13 @@ ARCH = "gfx950"
 
 SOURCES = ["coa_kernels.hip", "coa_halved.hip", "coa_batch.hip", "coa_committee.hip", "coa_cert_lat.hip", "coa_keybuild.hip", "coa_msm.hip", "coa_latency.hip",
            "coa_protocol.hip", "coa_resolve.hip", "coa_wire_dev.hip", "coa_wire_dev.cpp", "coa_engine.cpp", "coa_sig.cpp", "coa_dag.cpp", "coa_queue.cpp", "coa_queue_hip.cpp",
-           "coa_wire.cpp", "coa_cpu.cpp"]
+           "coa_wire.cpp", "coa_wire_cpu.cpp", "coa_cpu.cpp"]
 HEADERS = ["coa_fe.h", "coa_sc.h", "coa_ge.h", "coa_sha512.h", "coa_smul.h", "coa_kernels.h", "coa_batch.h", "coa_halved.h",
            "coa_committee.h", "coa_msm.h", "coa_fe_wave.h", "coa_ge_rows.h", "coa_halve.h", "coa_keycache.h",
            "coa_latency.h", "coa_queue.h", "coa_rcmp.h", "coa_lehmer.h", "coa_ge_sums.h", "coa_protocol.h",
            "coa_protocol_dev.h", "coa_prot_scan.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
            "coa_hostpool.h", "coa_job_bits.h", "coa_cert_scratch.h", "coa_lat_job.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge_dec29.h", "coa_ge29.h",
-           "coa_batch_dev.h", "coa_resolve.h", "coa_resolve_ws.h", "coa_wire_parse.h", "coa_wire_dev.h"]
+           "coa_batch_dev.h", "coa_resolve.h", "coa_resolve_ws.h", "coa_wire_parse.h", "coa_wire_dev.h", "coa_wire_mixed.h"]
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffunction-sections", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 
 

@@ -392,6 +392,23 @@ def verdict_votes(votes, committee=None, cpu=False):
     return [_dag_error(w, None, None, v.author) for w, v in zip(words, votes)]
 
 
+def verdict_frames(frames, rng_seed=0):
+    """dispatch-then-verify for a receive buffer of interleaved PrimaryMessage
+    frames, from ONE coa_wire_verdict_many call (the registered committee's
+    stakes and worker ids): per frame (kind, code, vote_index) -- kind MSG_* or
+    a negative WIRE_E*; code the DAG_* code of Header::verify / Vote::verify /
+    Certificate::verify (DAG_OK: Ok), or None for a certificate request and
+    for a frame the reference drops; vote_index the offending vote of
+    DAG_AUTHORITY_REUSE / DAG_UNKNOWN_VOTER, else 0.  The messages themselves
+    are not built: a caller that wants the reference's error object decodes
+    the frames it cares about."""
+    if not frames:
+        return []
+    kinds, words = coa_crypto.wire_verdict_many(frames, rng_seed=rng_seed)
+    return [(int(k), None, 0) if w == coa_crypto.DAG_NO_MESSAGE else (int(k), int(w) & 0xff, int(w) >> 8)
+            for k, w in zip(kinds, words)]
+
+
 def _committee_tuple(committee):
     names = committee.authorities()
     return (np.array([list(bytes(k)) for k in names], np.uint8).reshape(-1, 32), [committee.stakes[k] for k in names],

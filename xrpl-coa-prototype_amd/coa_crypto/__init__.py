@@ -158,6 +158,11 @@ def lib():
         "coa_wire_certificate_verdict_many": ([P8, P64, sz, ctypes.c_uint64, vp, vp], ctypes.c_int),
         "coa_wire_header_verdict_many": ([P8, P64, sz, vp, vp], ctypes.c_int),
         "coa_wire_vote_verdict_many": ([P8, P64, sz, vp, vp], ctypes.c_int),
+        "coa_wire_mixed_workspace_bytes": ([sz, sz], sz),
+        "coa_wire_decode_mixed_device": ([ctypes.c_int, vp, vp, sz, sz] + [vp] * 27, ctypes.c_int),
+        "coa_wire_verdict_many": ([P8, P64, sz, ctypes.c_uint64, vp, vp], ctypes.c_int),
+        "coa_cpu_wire_verdict_many": ([P8, P64, sz, ctypes.c_uint64, P8, vp, vp, P64, sz, vp, vp, ctypes.c_int],
+                                      ctypes.c_int),
         # the engine's own CPU path (explicit only; never a silent fallback)
         "coa_cpu_ed25519_verify_strict": ([P8, sz, P8, P8], ctypes.c_int),
         "coa_cpu_ed25519_verify_strict_many": ([P8, sz, P8, P8, sz, P8, ctypes.c_int], ctypes.c_int),
@@ -1213,6 +1218,62 @@ def wire_header_verdict_many(frames):
 
 def wire_vote_verdict_many(frames):
     return _wire_verdicts(lib().coa_wire_vote_verdict_many, frames)
+
+
+# ------------------------------------------- mixed batches on the device (f4)
+WIRE_NO_SLOT = 0xffffffff
+WIRE_MIXED_SET_NAMES = {
+    MSG_HEADER: ("hdata", "hoff", "ids", "authors", "sigs", "pcounts", "rounds"),
+    MSG_VOTE: ("ids", "rounds", "origins", "authors", "sigs"),
+    MSG_CERTIFICATE: ("hdata", "hoff", "ids", "origins", "hsigs", "rounds", "vpks", "vsigs", "voff", "pcounts"),
+}
+
+
+def wire_mixed_workspace_bytes(n, frame_bytes):
+    return lib().coa_wire_mixed_workspace_bytes(n, frame_bytes)
+
+
+def wire_decode_mixed_device(device, frames, offsets, headers, votes, certificates, kinds, slots, totals,
+                             frame_bytes=None, stream=None, workspace=None):
+    """One batch of interleaved frames in device memory -> each kind's frames,
+    compacted in frame order, in that kind's array set.  headers, votes,
+    certificates: dicts of torch tensors named by WIRE_MIXED_SET_NAMES -- the
+    arrays, in the order, of wire_decode_headers_device / _votes_device /
+    _certificates_device, each at the capacity that call states.  kinds
+    (int32 [n]), slots (int32 [n] holding uint32: the frame's rank among the
+    frames of its kind, WIRE_NO_SLOT where it has none), totals (int64 [8]):
+    headers, their header bytes, votes, certificates, their header bytes,
+    their votes, frames without a slot, 0."""
+    fb = frames.shape[0] if frame_bytes is None else frame_bytes
+    sets = []
+    for kind, d in ((MSG_HEADER, headers), (MSG_VOTE, votes), (MSG_CERTIFICATE, certificates)):
+        sets += [d[name].data_ptr() for name in WIRE_MIXED_SET_NAMES[kind]]
+    _check(lib().coa_wire_decode_mixed_device(device, frames.data_ptr(), offsets.data_ptr(), kinds.shape[0], fb, *sets,
+                                              kinds.data_ptr(), slots.data_ptr(), totals.data_ptr(), _ptr(workspace),
+                                              _handle(device, stream)))
+
+
+def wire_verdict_many(frames, rng_seed=0):
+    """Raw PrimaryMessage frames of every kind, interleaved -> (kinds int32 [n],
+    DAG_* words uint32 [n]): one upload, the partition by kind and the decode
+    on the device, Header::verify / Vote::verify / Certificate::verify over
+    each kind's frames, the words back in frame order; DAG_NO_MESSAGE for a
+    certificate request and for a frame that does not decode."""
+    return _wire_verdicts(lib().coa_wire_verdict_many, frames, rng_seed)
+
+
+def cpu_wire_verdict_many(frames, committee, rng_seed=0, nthreads=0):
+    """CPU path of wire_verdict_many (explicit only; no coa_init needed).
+    committee = (pks, stakes, workers).  No entry cap: a frame the device
+    reports as WIRE_ECAPACITY is answered as its real kind."""
+    n = len(frames)
+    data, offs = _frames(frames)
+    cp, cs, cw, co, cn = _committee_arrays(*committee)
+    kinds = np.zeros(max(n, 1), np.int32)
+    words = np.full(max(n, 1), 0xffffffff, np.uint32)
+    _check(lib().coa_cpu_wire_verdict_many(_u8p(data), _u64p(offs), n, rng_seed, _u8p(cp), _u8p(cs), _u8p(cw),
+                                           _u64p(co), cn, _u8p(kinds), _u8p(words), nthreads))
+    return kinds[:n], words[:n]
 
 
 # --------------------------------------------------------- aggregation queue

@@ -168,6 +168,157 @@ int wire_fused(int32_t want, const uint8_t* frames, const uint64_t* offs, size_t
   });
 }
 
+// ---- mixed batches
+void mixed_carve(WireMixedArgs& a, void* ws) {
+  const WireMixedWs L(a.n);
+  uint8_t* base = static_cast<uint8_t*>(ws);
+  a.hb = reinterpret_cast<uint64_t*>(base + L.hb);
+  a.nv = reinterpret_cast<uint64_t*>(base + L.nv);
+  a.bt = reinterpret_cast<uint64_t*>(base + L.bt);
+}
+
+// One kind's arrays in the device block of a mixed fused call; a vote has no
+// header data, a header no votes.
+enum { mHdata, mHoff, mIds, mAuthors, mOrigins, mSigs, mRounds, mPcounts, mVpks, mVsigs, mVoff, mWords, mSetSections };
+
+// offsets | frames (one H2D) | the three array sets at their stated capacities
+// | totals | slots | kinds | words in frame order (kinds and words: one D2H) |
+// the decoder's workspace.
+struct MixedLayout {
+  size_t offs = 0, frames = 0, set[COA_WIRE_MIXED_KINDS][mSetSections] = {}, totals = 0, slots = 0, kinds = 0, words = 0,
+         ws = 0, bytes = 0;
+  MixedLayout(size_t n, size_t fb) {
+    size_t end = 0;
+    auto take = [&end](size_t b) {
+      const size_t at_ = end;
+      end = align_up(at_ + b, 256);
+      return at_;
+    };
+    offs = take((n + 1) * 8);
+    frames = take(fb + 4);
+    const size_t votes = COA_WIRE_VOTES_BOUND(fb);
+    for (int k = 0; k < COA_WIRE_MIXED_KINDS; k++) {
+      size_t* at = set[k];
+      const bool hdr = k != COA_MSG_VOTE, cert = k == COA_MSG_CERTIFICATE;
+      at[mHdata] = take(hdr ? fb + 16 : 0);
+      at[mHoff] = take(hdr ? (n + 1) * 8 : 0);
+      at[mIds] = take(n * 32);
+      at[mAuthors] = take(n * 32);
+      at[mOrigins] = take(hdr ? 0 : n * 32);
+      at[mSigs] = take(n * 64);
+      at[mRounds] = take(n * 8);
+      at[mPcounts] = take(hdr ? n * 4 : 0);
+      at[mVpks] = take(cert ? votes * 32 + 16 : 0);
+      at[mVsigs] = take(cert ? votes * 64 + 16 : 0);
+      at[mVoff] = take(cert ? (n + 1) * 8 : 0);
+      at[mWords] = take(n * 4);
+    }
+    totals = take(COA_WIRE_MIXED_TOTALS * 8);
+    slots = take(n * 4);
+    kinds = take(n * 4);
+    words = take(n * 4);
+    ws = take(WireMixedWs(n).bytes);
+    bytes = end;
+  }
+};
+
+int wire_fused_mixed(const uint8_t* frames, const uint64_t* offs, size_t n, uint64_t rng_seed, int32_t* kinds_out,
+                     uint32_t* verdicts_out) {
+  if (n == 0) return COA_OK;
+  if (!offs || !kinds_out || !verdicts_out) return fail(COA_EINVAL, "null argument");
+  if (!offsets_monotone(offs, n)) return fail(COA_EINVAL, "offsets not monotone");
+  const size_t fb = offs[n];
+  if (fb && !frames) return fail(COA_EINVAL, "null frames");
+  if (check_n(n) != COA_OK || check_n(fb) != COA_OK) return COA_EINVAL;
+  const int rc0 = ensure_init();
+  if (rc0 != COA_OK) return rc0;
+  // one context per call: a single shard, under its context's lock
+  return for_shards(1, [&](Dev& d, size_t, size_t) -> int {
+    hipStream_t s = d.stream;
+    // what each verdict call below answers itself; here also for a batch that holds no message
+    if (!keys_now(d)->has_prot) return fail(COA_EINVAL, "committee registered without stakes");
+    const MixedLayout L(n, fb);
+    const size_t back = L.words - L.kinds + n * 4;  // kinds | words
+    HIP_TRY(d.pin.ensure(std::max(L.frames + fb + 4, back)));
+    HIP_TRY(d.out.ensure(L.bytes));
+    uint8_t* h = static_cast<uint8_t*>(d.pin.p);
+    uint8_t* b = d.out.as<uint8_t>();
+    const Seg segs[2] = {{h + L.offs, offs, (n + 1) * 8}, {h + L.frames, frames, fb}};
+    CopyPool::get().copy(segs, fb ? 2 : 1);
+    HIP_TRY(hipMemcpyAsync(b, h, L.frames + fb, hipMemcpyHostToDevice, s));
+    int32_t* d_kinds = reinterpret_cast<int32_t*>(b + L.kinds);
+    uint32_t* d_slots = reinterpret_cast<uint32_t*>(b + L.slots);
+    WireMixedArgs a{};
+    a.frames = b + L.frames;
+    a.offs = reinterpret_cast<const uint64_t*>(b + L.offs);
+    a.frame_bytes = fb;
+    a.n = (uint32_t)n;
+    a.kinds = d_kinds;
+    a.slots = d_slots;
+    a.totals = reinterpret_cast<uint64_t*>(b + L.totals);
+    auto u8 = [&](int k, int sec) { return b + L.set[k][sec]; };
+    auto u64 = [&](int k, int sec) { return reinterpret_cast<uint64_t*>(b + L.set[k][sec]); };
+    auto u32 = [&](int k, int sec) { return reinterpret_cast<uint32_t*>(b + L.set[k][sec]); };
+    for (int k = 0; k < COA_WIRE_MIXED_KINDS; k++) {
+      WireSet& o = a.set[k];
+      o.ids = u8(k, mIds);
+      o.authors = u8(k, mAuthors);
+      o.sigs = u8(k, mSigs);
+      o.rounds = u64(k, mRounds);
+      if (k == COA_MSG_VOTE) {
+        o.vorigins = u8(k, mOrigins);
+        continue;
+      }
+      o.hdata = u8(k, mHdata);
+      o.hoff = u64(k, mHoff);
+      o.pcounts = u32(k, mPcounts);
+      if (k == COA_MSG_CERTIFICATE) {
+        o.vpks = u8(k, mVpks);
+        o.vsigs = u8(k, mVsigs);
+        o.voff = u64(k, mVoff);
+      }
+    }
+    mixed_carve(a, b + L.ws);
+    HIP_TRY(coa_launch_wire_decode_mixed(a, s));
+    // the verdict calls take their counts, the certificate call its votes, as host arguments
+    uint64_t* totals = reinterpret_cast<uint64_t*>(h);
+    HIP_TRY(hipMemcpyAsync(totals, a.totals, COA_WIRE_MIXED_TOTALS * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const size_t nh = (size_t)totals[0], nvt = (size_t)totals[2], nc = (size_t)totals[3], cvotes = (size_t)totals[5];
+    size_t need = 0;
+    if (nh) need = std::max(need, coa_message_verdict_workspace_bytes(nh));
+    if (nvt) need = std::max(need, coa_message_verdict_workspace_bytes(nvt));
+    if (nc) need = std::max({need, coa_certificate_verdict_workspace_bytes(nc, cvotes), ResolveWs(nc, cvotes, 0).bytes});
+    if (need) HIP_TRY(d.vws.ensure(need));  // one workspace: the calls follow each other on s
+    int rc = COA_OK;
+    const int H = COA_MSG_HEADER, V = COA_MSG_VOTE, C = COA_MSG_CERTIFICATE;
+    if (nh)
+      rc = coa_header_verdict_many_device(d.id, u8(H, mHdata), u64(H, mHoff), u8(H, mIds), u8(H, mAuthors), u8(H, mSigs),
+                                          nh, u32(H, mPcounts), u32(H, mWords), d.vws.p, s);
+    if (rc == COA_OK && nvt)
+      rc = coa_vote_verdict_many_device(d.id, u8(V, mIds), u64(V, mRounds), u8(V, mOrigins), u8(V, mAuthors),
+                                        u8(V, mSigs), nvt, u32(V, mWords), d.vws.p, s);
+    if (rc == COA_OK && nc) {
+      rc = coa_certificate_verdict_many_device(d.id, u8(C, mHdata), u64(C, mHoff), u8(C, mIds), u8(C, mAuthors),
+                                               u8(C, mSigs), u64(C, mRounds), u8(C, mVpks), u8(C, mVsigs), u64(C, mVoff),
+                                               nc, cvotes, u32(C, mPcounts), u32(C, mWords), d.vws.p, s);
+      if (rc == COA_OK)
+        rc = coa_certificate_votes_resolve_device(d.id, u8(C, mIds), u8(C, mAuthors), u64(C, mRounds), u8(C, mVpks),
+                                                  u8(C, mVsigs), u64(C, mVoff), nc, cvotes, 0, nullptr, rng_seed,
+                                                  u32(C, mWords), nullptr, d.vws.p, s);
+    }
+    if (rc != COA_OK) return rc;
+    uint32_t* d_words = reinterpret_cast<uint32_t*>(b + L.words);
+    HIP_TRY(coa_launch_wire_scatter(d_kinds, d_slots, u32(H, mWords), u32(V, mWords), u32(C, mWords), d_words,
+                                    (uint32_t)n, s));
+    HIP_TRY(hipMemcpyAsync(h, d_kinds, back, hipMemcpyDeviceToHost, s));  // kinds and words lie side by side: one D2H
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(kinds_out, h, n * 4);
+    std::memcpy(verdicts_out, h + (L.words - L.kinds), n * 4);
+    return COA_OK;
+  });
+}
+
 }  // namespace coa_rt
 
 using namespace coa_rt;
@@ -272,6 +423,75 @@ int coa_wire_decode_votes_device(int device, const uint8_t* d_frames, const uint
   a.sigs = d_sigs;
   a.totals = d_totals;
   return wire_decode(*d, s, a, workspace);
+}
+
+size_t coa_wire_mixed_workspace_bytes(size_t n, size_t frame_bytes) {
+  (void)frame_bytes;  // as coa_wire_workspace_bytes
+  return WireMixedWs(n).bytes;
+}
+
+int coa_wire_decode_mixed_device(int device, const uint8_t* d_frames, const uint64_t* d_frame_offsets, size_t n,
+                                 size_t frame_bytes, uint8_t* d_h_header_data, uint64_t* d_h_header_offsets,
+                                 uint8_t* d_h_ids, uint8_t* d_h_authors, uint8_t* d_h_sigs,
+                                 uint32_t* d_h_payload_counts, uint64_t* d_h_rounds, uint8_t* d_v_ids,
+                                 uint64_t* d_v_rounds, uint8_t* d_v_origins, uint8_t* d_v_authors, uint8_t* d_v_sigs,
+                                 uint8_t* d_c_header_data, uint64_t* d_c_header_offsets, uint8_t* d_c_ids,
+                                 uint8_t* d_c_origins, uint8_t* d_c_header_sigs, uint64_t* d_c_rounds,
+                                 uint8_t* d_c_vote_pks, uint8_t* d_c_vote_sigs, uint64_t* d_c_vote_offsets,
+                                 uint32_t* d_c_payload_counts, int32_t* d_kinds, uint32_t* d_slots,
+                                 uint64_t* d_totals, void* workspace, void* stream) {
+  if (n == 0) return COA_OK;
+  Dev* d;
+  hipStream_t s;
+  const bool ok = d_h_header_data && d_h_header_offsets && d_h_ids && d_h_authors && d_h_sigs && d_h_payload_counts &&
+                  d_h_rounds && d_v_ids && d_v_rounds && d_v_origins && d_v_authors && d_v_sigs && d_c_header_data &&
+                  d_c_header_offsets && d_c_ids && d_c_origins && d_c_header_sigs && d_c_rounds && d_c_vote_pks &&
+                  d_c_vote_sigs && d_c_vote_offsets && d_c_payload_counts && d_kinds && d_slots && d_totals;
+  if (const int e = wire_enter(device, d_frames, d_frame_offsets, n, frame_bytes, ok, stream, d, s)) return e;
+  WireMixedArgs a{};
+  a.frames = d_frames;
+  a.offs = d_frame_offsets;
+  a.frame_bytes = frame_bytes;
+  a.n = (uint32_t)n;
+  a.kinds = d_kinds;
+  a.slots = d_slots;
+  a.totals = d_totals;
+  WireSet& h = a.set[COA_MSG_HEADER];
+  h.hdata = d_h_header_data;
+  h.hoff = d_h_header_offsets;
+  h.ids = d_h_ids;
+  h.authors = d_h_authors;
+  h.sigs = d_h_sigs;
+  h.pcounts = d_h_payload_counts;
+  h.rounds = d_h_rounds;
+  WireSet& v = a.set[COA_MSG_VOTE];
+  v.ids = d_v_ids;
+  v.rounds = d_v_rounds;
+  v.vorigins = d_v_origins;
+  v.authors = d_v_authors;
+  v.sigs = d_v_sigs;
+  WireSet& c = a.set[COA_MSG_CERTIFICATE];
+  c.hdata = d_c_header_data;
+  c.hoff = d_c_header_offsets;
+  c.ids = d_c_ids;
+  c.authors = d_c_origins;
+  c.sigs = d_c_header_sigs;
+  c.rounds = d_c_rounds;
+  c.vpks = d_c_vote_pks;
+  c.vsigs = d_c_vote_sigs;
+  c.voff = d_c_vote_offsets;
+  c.pcounts = d_c_payload_counts;
+  // no key-cache generation to trail: the decode reads no committee table
+  return with_workspace(*d, s, workspace, d->vws, WireMixedWs(n).bytes, nullptr, [&](void* ws) -> int {
+    mixed_carve(a, ws);
+    HIP_TRY(coa_launch_wire_decode_mixed(a, s));
+    return COA_OK;
+  });
+}
+
+int coa_wire_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n, uint64_t rng_seed,
+                          int32_t* kinds_out, uint32_t* verdicts_out) {
+  return wire_fused_mixed(frames, frame_offsets, n, rng_seed, kinds_out, verdicts_out);
 }
 
 int coa_wire_certificate_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n,

@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "coa_wire_mixed.h"  // WireMixedWs: the mixed mode's workspace, host-only
+
 #define COA_WIRE_SCAN_BLOCK 256u  // frames per block of the prefix-sum kernels
 
 // per-frame header bytes [n] | per-frame votes [n] | three block totals per
@@ -51,7 +53,45 @@ struct WireArgs {
   uint64_t* totals;   // 4
 };
 
+// The mixed mode: one array set per kind (the fields of WireArgs' decode part,
+// item k of kind's set is the k-th frame of the kind), a slot per frame.
+struct WireSet {
+  uint8_t* hdata;
+  uint64_t* hoff;  // count + 1 used, n + 1 provided
+  uint8_t* ids;
+  uint8_t* authors;
+  uint8_t* sigs;
+  uint64_t* rounds;
+  uint32_t* pcounts;
+  uint8_t* vpks;
+  uint8_t* vsigs;
+  uint64_t* voff;
+  uint8_t* vorigins;
+};
+
+struct WireMixedArgs {
+  const uint8_t* frames;
+  const uint64_t* offs;  // n + 1
+  uint64_t frame_bytes;
+  uint32_t n;
+  int32_t* kinds;
+  uint64_t* hb;
+  uint64_t* nv;
+  WireSet set[COA_WIRE_MIXED_KINDS];  // by COA_MSG_HEADER, COA_MSG_VOTE, COA_MSG_CERTIFICATE
+  uint32_t* slots;   // n
+  uint64_t* bt;      // COA_WIRE_MIXED_SUMS * blocks
+  uint64_t* totals;  // COA_WIRE_MIXED_TOTALS
+};
+static_assert(COA_WIRE_MIXED_BLOCK == COA_WIRE_SCAN_BLOCK, "one block size for both modes' prefix sums");
+
 // k_wire_scan on s: kinds, hb and nv of every frame.
 hipError_t coa_launch_wire_scan(const WireArgs& a, hipStream_t s);
 // The scan, the three prefix-sum launches and k_wire_decode on s.
 hipError_t coa_launch_wire_decode(const WireArgs& a, hipStream_t s);
+// The scan, the three prefix-sum launches over six quantities and
+// k_wire_decode_mixed on s.
+hipError_t coa_launch_wire_decode_mixed(const WireMixedArgs& a, hipStream_t s);
+// out[i] = words[kinds[i]][slots[i]], COA_DAG_NO_MESSAGE where frame i has no slot.
+hipError_t coa_launch_wire_scatter(const int32_t* kinds, const uint32_t* slots, const uint32_t* header_words,
+                                   const uint32_t* vote_words, const uint32_t* certificate_words, uint32_t* out,
+                                   uint32_t n, hipStream_t s);

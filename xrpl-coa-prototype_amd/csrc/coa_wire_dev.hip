@@ -11,6 +11,11 @@
 //                   frames of the call's kind, as three launches: no kernel
 //                   waits for another workgroup
 //   k_wire_decode   one wavefront per frame: the fields into the output arrays
+//   k_wire_decode_mixed / k_wire_scatter
+//                   the mixed mode: the sums run over six quantities (every
+//                   kind's frames, header bytes and votes), a frame's fields
+//                   go to its slot in its kind's arrays, and the verdict
+//                   words come back to frame order
 //
 // A frame of up to kStage bytes is copied into LDS first (dword loads between
 // the unaligned ends) and every rule then reads LDS; a longer frame is read
@@ -26,6 +31,7 @@
 namespace {
 
 constexpr uint32_t kWaves = 4;       // frames per block
+constexpr uint32_t kMixedWaves = 1;  // frames per block of k_wire_decode_mixed: neighbours differ in kind and length, and a block's LDS is held for its longest frame
 constexpr uint32_t kStage = 12288;   // LDS bytes per frame: a 67-vote, 67-parent, 32-payload certificate is 11.3 KB
 
 __device__ __forceinline__ void wave_sync() {
@@ -155,114 +161,181 @@ __global__ void __launch_bounds__(64 * kWaves) k_wire_scan(const WireArgs a) {
   }
 }
 
-// What frame i adds to the call's sums: header bytes, votes, one frame.
-__device__ __forceinline__ void contribution(const WireArgs& a, uint32_t i, uint64_t v[3]) {
-  const bool mine = i < a.n && a.kinds[i] == a.want;
-  v[0] = mine && a.want != COA_MSG_VOTE ? a.hb[i] : 0;
-  v[1] = mine && a.want == COA_MSG_CERTIFICATE ? a.nv[i] : 0;
-  v[2] = mine ? 1 : 0;
-}
-
-// Exclusive scan of v over the block's COA_WIRE_SCAN_BLOCK threads.
-__device__ void block_scan(const uint64_t v[3], uint64_t (*sh)[COA_WIRE_SCAN_BLOCK], uint64_t excl[3], uint64_t total[3]) {
-  const uint32_t t = threadIdx.x;
-  for (int q = 0; q < 3; q++) sh[q][t] = v[q];
-  __syncthreads();
-  for (uint32_t o = 1; o < COA_WIRE_SCAN_BLOCK; o <<= 1) {
-    uint64_t x[3];
-    for (int q = 0; q < 3; q++) x[q] = t >= o ? sh[q][t - o] : 0;
-    __syncthreads();
-    for (int q = 0; q < 3; q++) sh[q][t] += x[q];
-    __syncthreads();
+// What the prefix sums run over.  One kind (the index-aligned decoders): three
+// quantities of the frames of a.want.
+struct SumsOne {
+  static constexpr int Q = 3;
+  using Args = WireArgs;
+  // What frame i adds to the call's sums: header bytes, votes, one frame.
+  static __device__ __forceinline__ void contribution(const WireArgs& a, uint32_t i, uint64_t v[3]) {
+    const bool mine = i < a.n && a.kinds[i] == a.want;
+    v[0] = mine && a.want != COA_MSG_VOTE ? a.hb[i] : 0;
+    v[1] = mine && a.want == COA_MSG_CERTIFICATE ? a.nv[i] : 0;
+    v[2] = mine ? 1 : 0;
   }
-  for (int q = 0; q < 3; q++) {
-    excl[q] = sh[q][t] - v[q];
-    total[q] = sh[q][COA_WIRE_SCAN_BLOCK - 1];
-  }
-}
-
-__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_block_totals(const WireArgs a) {
-  __shared__ uint64_t sh[3][COA_WIRE_SCAN_BLOCK];
-  uint64_t v[3], excl[3], total[3];
-  contribution(a, blockIdx.x * COA_WIRE_SCAN_BLOCK + threadIdx.x, v);
-  block_scan(v, sh, excl, total);
-  if (threadIdx.x < 3) a.bt[(size_t)blockIdx.x * 3 + threadIdx.x] = total[threadIdx.x];
-}
-
-// One block: the block totals become their exclusive prefixes in place, and
-// the call's totals are written.
-__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_scan_totals(const WireArgs a, uint32_t blocks) {
-  __shared__ uint64_t sh[3][COA_WIRE_SCAN_BLOCK];
-  const uint32_t per = (blocks + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK;
-  const uint32_t lo = min(blocks, threadIdx.x * per), hi = min(blocks, lo + per);
-  uint64_t v[3] = {0, 0, 0}, excl[3], total[3];
-  for (uint32_t b = lo; b < hi; b++)
-    for (int q = 0; q < 3; q++) v[q] += a.bt[(size_t)b * 3 + q];
-  block_scan(v, sh, excl, total);
-  for (uint32_t b = lo; b < hi; b++)
-    for (int q = 0; q < 3; q++) {
-      const uint64_t t = a.bt[(size_t)b * 3 + q];
-      a.bt[(size_t)b * 3 + q] = excl[q];
-      excl[q] += t;
-    }
-  if (threadIdx.x == 0 && a.totals) {
+  static __device__ __forceinline__ void totals(const WireArgs& a, const uint64_t total[3]) {
+    if (!a.totals) return;
     a.totals[0] = total[0];
     a.totals[1] = total[1];
     a.totals[2] = total[2];
     a.totals[3] = a.n - total[2];
   }
+  // Frame i's place: its exclusive sums `at`, its own contribution v.
+  static __device__ __forceinline__ void place(const WireArgs& a, uint32_t i, const uint64_t at[3], const uint64_t v[3]) {
+    if (a.hoff) {
+      a.hoff[i] = at[0];
+      if (i == a.n - 1) a.hoff[a.n] = at[0] + v[0];
+    }
+    if (a.voff) {
+      a.voff[i] = at[1];
+      if (i == a.n - 1) a.voff[a.n] = at[1] + v[1];
+    }
+  }
+};
+
+// Every kind at once (the mixed mode): headers and their bytes | votes |
+// certificates, their bytes and their votes -- the first six words of the
+// call's totals.
+struct SumsMixed {
+  static constexpr int Q = COA_WIRE_MIXED_SUMS;
+  using Args = WireMixedArgs;
+  static __device__ __forceinline__ void contribution(const WireMixedArgs& a, uint32_t i, uint64_t v[6]) {
+    const int32_t kind = i < a.n ? a.kinds[i] : -1;
+    const bool h = kind == COA_MSG_HEADER, c = kind == COA_MSG_CERTIFICATE;
+    v[0] = h;
+    v[1] = h ? a.hb[i] : 0;
+    v[2] = kind == COA_MSG_VOTE;
+    v[3] = c;
+    v[4] = c ? a.hb[i] : 0;
+    v[5] = c ? a.nv[i] : 0;
+  }
+  // The totals, and each kind's offsets at its count: the offsets are defined
+  // on [0, count], also where the count is 0.
+  static __device__ __forceinline__ void totals(const WireMixedArgs& a, const uint64_t total[6]) {
+    for (int q = 0; q < 6; q++) a.totals[q] = total[q];
+    a.totals[6] = a.n - (total[0] + total[2] + total[3]);
+    a.totals[7] = 0;
+    a.set[COA_MSG_HEADER].hoff[total[0]] = total[1];
+    a.set[COA_MSG_CERTIFICATE].hoff[total[3]] = total[4];
+    a.set[COA_MSG_CERTIFICATE].voff[total[3]] = total[5];
+  }
+  // The slot: the frame's rank among the frames of its kind (the partition
+  // is stable); a header's and a certificate's offsets at their slot.
+  static __device__ __forceinline__ void place(const WireMixedArgs& a, uint32_t i, const uint64_t at[6], const uint64_t v[6]) {
+    uint32_t slot = COA_WIRE_NO_SLOT;
+    if (v[0]) {
+      slot = (uint32_t)at[0];
+      a.set[COA_MSG_HEADER].hoff[slot] = at[1];
+    } else if (v[2]) {
+      slot = (uint32_t)at[2];
+    } else if (v[3]) {
+      slot = (uint32_t)at[3];
+      a.set[COA_MSG_CERTIFICATE].hoff[slot] = at[4];
+      a.set[COA_MSG_CERTIFICATE].voff[slot] = at[5];
+    }
+    a.slots[i] = slot;
+  }
+};
+
+// Exclusive scan of v over the block's COA_WIRE_SCAN_BLOCK threads.
+template <int Q>
+__device__ void block_scan(const uint64_t v[Q], uint64_t (*sh)[COA_WIRE_SCAN_BLOCK], uint64_t excl[Q], uint64_t total[Q]) {
+  const uint32_t t = threadIdx.x;
+  for (int q = 0; q < Q; q++) sh[q][t] = v[q];
+  __syncthreads();
+  for (uint32_t o = 1; o < COA_WIRE_SCAN_BLOCK; o <<= 1) {
+    uint64_t x[Q];
+    for (int q = 0; q < Q; q++) x[q] = t >= o ? sh[q][t - o] : 0;
+    __syncthreads();
+    for (int q = 0; q < Q; q++) sh[q][t] += x[q];
+    __syncthreads();
+  }
+  for (int q = 0; q < Q; q++) {
+    excl[q] = sh[q][t] - v[q];
+    total[q] = sh[q][COA_WIRE_SCAN_BLOCK - 1];
+  }
 }
 
-__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_add(const WireArgs a) {
-  __shared__ uint64_t sh[3][COA_WIRE_SCAN_BLOCK];
+template <class M>
+__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_block_totals(const typename M::Args a) {
+  constexpr int Q = M::Q;
+  __shared__ uint64_t sh[Q][COA_WIRE_SCAN_BLOCK];
+  uint64_t v[Q], excl[Q], total[Q];
+  M::contribution(a, blockIdx.x * COA_WIRE_SCAN_BLOCK + threadIdx.x, v);
+  block_scan<Q>(v, sh, excl, total);
+  if (threadIdx.x < Q) a.bt[(size_t)blockIdx.x * Q + threadIdx.x] = total[threadIdx.x];
+}
+
+// One block: the block totals become their exclusive prefixes in place, and
+// the call's totals are written.
+template <class M>
+__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_scan_totals(const typename M::Args a, uint32_t blocks) {
+  constexpr int Q = M::Q;
+  __shared__ uint64_t sh[Q][COA_WIRE_SCAN_BLOCK];
+  const uint32_t per = (blocks + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK;
+  const uint32_t lo = min(blocks, threadIdx.x * per), hi = min(blocks, lo + per);
+  uint64_t v[Q] = {}, excl[Q], total[Q];
+  for (uint32_t b = lo; b < hi; b++)
+    for (int q = 0; q < Q; q++) v[q] += a.bt[(size_t)b * Q + q];
+  block_scan<Q>(v, sh, excl, total);
+  for (uint32_t b = lo; b < hi; b++)
+    for (int q = 0; q < Q; q++) {
+      const uint64_t t = a.bt[(size_t)b * Q + q];
+      a.bt[(size_t)b * Q + q] = excl[q];
+      excl[q] += t;
+    }
+  if (threadIdx.x == 0) M::totals(a, total);
+}
+
+template <class M>
+__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_add(const typename M::Args a) {
+  constexpr int Q = M::Q;
+  __shared__ uint64_t sh[Q][COA_WIRE_SCAN_BLOCK];
   const uint32_t i = blockIdx.x * COA_WIRE_SCAN_BLOCK + threadIdx.x;
-  uint64_t v[3], excl[3], total[3];
-  contribution(a, i, v);
-  block_scan(v, sh, excl, total);
+  uint64_t v[Q], excl[Q], total[Q];
+  M::contribution(a, i, v);
+  block_scan<Q>(v, sh, excl, total);
   if (i >= a.n) return;
-  const uint64_t h = a.bt[(size_t)blockIdx.x * 3] + excl[0], w = a.bt[(size_t)blockIdx.x * 3 + 1] + excl[1];
-  if (a.hoff) {
-    a.hoff[i] = h;
-    if (i == a.n - 1) a.hoff[a.n] = h + v[0];
-  }
-  if (a.voff) {
-    a.voff[i] = w;
-    if (i == a.n - 1) a.voff[a.n] = w + v[1];
-  }
+  for (int q = 0; q < Q; q++) excl[q] += a.bt[(size_t)blockIdx.x * Q + q];
+  M::place(a, i, excl, v);
 }
 
-// Frame i, known to be a well-formed message of kind a.want, into the arrays.
-__device__ __forceinline__ void decode_frame(const WireArgs& a, uint32_t i, const uint8_t* p, size_t len, uint32_t lane,
-                                             uint8_t* last) {
+// A frame known to be a well-formed message of kind `want` into item `item` of
+// the arrays o (WireArgs: item i is frame i; a WireSet of the mixed mode: the
+// frame's slot).
+template <class O>
+__device__ __forceinline__ void decode_frame(const O& o, int32_t want, uint32_t item, const uint8_t* p, size_t len,
+                                             uint32_t lane, uint8_t* last) {
   CoaWpFrame f;
   (void)coa_wp_walk(p, len, &f);
-  if (a.want == COA_MSG_VOTE) {
-    if (lane < 32) a.ids[(size_t)i * 32 + lane] = p[f.v_id + lane];
-    a.sigs[(size_t)i * 64 + lane] = p[f.v_sig + lane];
-    if (lane == 0) a.rounds[i] = f.v_round;
+  const size_t i = item;
+  if (want == COA_MSG_VOTE) {
+    if (lane < 32) o.ids[i * 32 + lane] = p[f.v_id + lane];
+    o.sigs[i * 64 + lane] = p[f.v_sig + lane];
+    if (lane == 0) o.rounds[i] = f.v_round;
     if (lane < 2) {
       size_t pos = lane ? f.v_author : f.v_origin;
-      (void)coa_wp_key(p, len, &pos, (lane ? a.authors : a.vorigins) + (size_t)i * 32);
+      (void)coa_wp_key(p, len, &pos, (lane ? o.authors : o.vorigins) + i * 32);
     }
     return;
   }
-  uint8_t* out = a.hdata + a.hoff[i];
-  if (lane < 32) a.ids[(size_t)i * 32 + lane] = p[f.id + lane];
-  a.sigs[(size_t)i * 64 + lane] = p[f.sig + lane];
+  uint8_t* out = o.hdata + o.hoff[i];
+  if (lane < 32) o.ids[i * 32 + lane] = p[f.id + lane];
+  o.sigs[i * 64 + lane] = p[f.sig + lane];
   if (lane < 2) {
     size_t pos = f.author;
-    (void)coa_wp_key(p, len, &pos, lane ? a.authors + (size_t)i * 32 : out);
+    (void)coa_wp_key(p, len, &pos, lane ? o.authors + i * 32 : out);
   }
-  if (lane == 2) a.rounds[i] = f.round;
+  if (lane == 2) o.rounds[i] = f.round;
   if (lane >= 8 && lane < 16) out[32 + (lane - 8)] = (uint8_t)(f.round >> (8 * (lane - 8)));
   const uint32_t P = set_last(p + f.payload, 36, (uint32_t)f.np, lane, last);
   set_emit(p + f.payload, 36, (uint32_t)f.np, lane, last, out + 40);
   (void)set_last(p + f.parents, 32, (uint32_t)f.nq, lane, last);
   set_emit(p + f.parents, 32, (uint32_t)f.nq, lane, last, out + 40 + 36 * (size_t)P);
-  if (lane == 0) a.pcounts[i] = P;
-  if (a.want == COA_MSG_CERTIFICATE) {
-    const uint64_t v0 = a.voff[i];
-    (void)votes_do(p, len, f, lane, a.vpks + v0 * 32, a.vsigs + v0 * 64);
+  if (lane == 0) o.pcounts[i] = P;
+  if (want == COA_MSG_CERTIFICATE) {
+    const uint64_t v0 = o.voff[i];
+    (void)votes_do(p, len, f, lane, o.vpks + v0 * 32, o.vsigs + v0 * 64);
   }
 }
 
@@ -286,9 +359,47 @@ __global__ void __launch_bounds__(64 * kWaves) k_wire_decode(const WireArgs a) {
   const uint64_t o0 = a.offs[i];
   const size_t len = (size_t)(a.offs[i + 1] - o0);
   if (len <= kStage)
-    decode_frame(a, i, stage_frame(a.frames + o0, (uint32_t)len, lane, stage[wave]), len, lane, last[wave]);
+    decode_frame(a, a.want, i, stage_frame(a.frames + o0, (uint32_t)len, lane, stage[wave]), len, lane, last[wave]);
   else
-    decode_frame(a, i, a.frames + o0, len, lane, last[wave]);
+    decode_frame(a, a.want, i, a.frames + o0, len, lane, last[wave]);
+}
+
+// The mixed mode: frame i of kind k into item slots[i] of kind k's arrays.  A
+// frame without a slot writes nothing: no placeholders, and nothing at or
+// above a kind's count.
+template <uint32_t W>
+__global__ void __launch_bounds__(64 * W) k_wire_decode_mixed(const WireMixedArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[W][kStage + 16];
+  __shared__ uint8_t last[W][COA_WIRE_DEV_MAX_ENTRIES];
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t i = blockIdx.x * W + wave;
+  if (i >= a.n) return;
+  const uint32_t slot = a.slots[i];
+  if (slot == COA_WIRE_NO_SLOT) return;
+  // the scan found the frame inside the buffer and well formed, of kind 0, 1 or 2
+  const int32_t kind = __builtin_amdgcn_readfirstlane(a.kinds[i]);
+  const WireSet& o = a.set[kind];
+  const uint64_t o0 = a.offs[i];
+  const size_t len = (size_t)(a.offs[i + 1] - o0);
+  if (len <= kStage)
+    decode_frame(o, kind, slot, stage_frame(a.frames + o0, (uint32_t)len, lane, stage[wave]), len, lane, last[wave]);
+  else
+    decode_frame(o, kind, slot, a.frames + o0, len, lane, last[wave]);
+}
+
+// One thread per frame: its item's word, or COA_DAG_NO_MESSAGE.
+__global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_scatter(const int32_t* kinds, const uint32_t* slots,
+                                                                       const uint32_t* w0, const uint32_t* w1,
+                                                                       const uint32_t* w2, uint32_t* out, uint32_t n) {
+  const uint32_t i = blockIdx.x * COA_WIRE_SCAN_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t slot = slots[i];
+  uint32_t w = COA_DAG_NO_MESSAGE;
+  if (slot != COA_WIRE_NO_SLOT) {
+    const int32_t kind = kinds[i];
+    w = (kind == COA_MSG_HEADER ? w0 : kind == COA_MSG_VOTE ? w1 : w2)[slot];
+  }
+  out[i] = w;
 }
 
 }  // namespace
@@ -303,9 +414,38 @@ hipError_t coa_launch_wire_decode(const WireArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   const uint32_t blocks = (a.n + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK;
   hipLaunchKernelGGL(k_wire_scan, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, a);
-  hipLaunchKernelGGL(k_wire_block_totals, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
-  hipLaunchKernelGGL(k_wire_scan_totals, dim3(1), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a, blocks);
-  hipLaunchKernelGGL(k_wire_add, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(k_wire_block_totals<SumsOne>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(k_wire_scan_totals<SumsOne>, dim3(1), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a, blocks);
+  hipLaunchKernelGGL(k_wire_add<SumsOne>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
   hipLaunchKernelGGL(k_wire_decode, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t coa_launch_wire_decode_mixed(const WireMixedArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  const uint32_t blocks = (a.n + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK;
+  WireArgs scan{};  // k_wire_scan as it is: kinds, hb and nv of every frame
+  scan.frames = a.frames;
+  scan.offs = a.offs;
+  scan.frame_bytes = a.frame_bytes;
+  scan.n = a.n;
+  scan.kinds = a.kinds;
+  scan.hb = a.hb;
+  scan.nv = a.nv;
+  hipLaunchKernelGGL(k_wire_scan, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, scan);
+  hipLaunchKernelGGL(k_wire_block_totals<SumsMixed>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(k_wire_scan_totals<SumsMixed>, dim3(1), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a, blocks);
+  hipLaunchKernelGGL(k_wire_add<SumsMixed>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
+  hipLaunchKernelGGL(k_wire_decode_mixed<kMixedWaves>, dim3((a.n + kMixedWaves - 1) / kMixedWaves), dim3(64 * kMixedWaves), 0,
+                     s, a);
+  return hipGetLastError();
+}
+
+hipError_t coa_launch_wire_scatter(const int32_t* kinds, const uint32_t* slots, const uint32_t* header_words,
+                                   const uint32_t* vote_words, const uint32_t* certificate_words, uint32_t* out,
+                                   uint32_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_wire_scatter, dim3((n + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK), dim3(COA_WIRE_SCAN_BLOCK), 0,
+                     s, kinds, slots, header_words, vote_words, certificate_words, out, n);
   return hipGetLastError();
 }
