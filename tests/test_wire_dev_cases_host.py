@@ -264,5 +264,5 @@ def test_constants_match_the_sources():
     csrc = os.path.join(ROOT, "xrpl-coa-prototype_amd", "csrc")
     hip = open(os.path.join(csrc, "coa_wire_dev.hip")).read()
     assert f"constexpr uint32_t kStage = {cases.STAGE};" in hip
-    assert f"#define COA_WIRE_SCAN_BLOCK {cases.SCAN_BLOCK}u" in open(os.path.join(csrc, "coa_wire_dev.h")).read()
+    assert f"#define COA_WIRE_SCAN_BLOCK {cases.SCAN_BLOCK}u" in open(os.path.join(csrc, "coa_wire_layout.h")).read()
     assert f"#define COA_WP_VOTE_STRIDE {cases.VOTE_STRIDE}u" in open(os.path.join(csrc, "coa_wire_parse.h")).read()

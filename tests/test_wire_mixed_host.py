@@ -8,7 +8,7 @@
   by the host scanner alone.
 * the return codes of the new entries before any device work, and the
   workspace size.
-* the host-only layout and partition header csrc/coa_wire_mixed.h under a
+* the host-only layout and partition header csrc/coa_wire_layout.h under a
   stand-alone program (tests/sanitize/wire_mixed_driver.cpp) built with
   -fsanitize=address,undefined and run as a child process."""
 import ctypes
@@ -251,4 +251,4 @@ def test_layout_and_partition_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     print(r.stdout, r.stderr)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.strip().endswith("ok 121 cases")
+    assert r.stdout.strip().endswith("ok 233 cases")

@@ -76,7 +76,7 @@ def kernels(csrc, names):
             # .Lpost_getpc<N> labels count through the whole file, not the function
             count, sha = dc.digest([(lab, op, s and re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc", s))
                                     for lab, op, s in dc.function_lines(text, sym + ":")])
-            name = re.sub(r"^void ", "", dem.split("(")[0])
+            name = re.sub(r"^void ", "", dem.replace("(anonymous namespace)::", "").split("(")[0])
             out[name] = dict(meta[sym], file=n, symbol=sym, instructions=count, text_sha256=sha)
     return out
 

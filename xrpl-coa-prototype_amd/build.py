@@ -26,7 +26,7 @@ HEADERS = ["coa_fe.h", "coa_sc.h", "coa_ge.h", "coa_sha512.h", "coa_smul.h", "co
            "coa_latency.h", "coa_queue.h", "coa_rcmp.h", "coa_lehmer.h", "coa_ge_sums.h", "coa_protocol.h",
            "coa_protocol_dev.h", "coa_prot_scan.h", "coa_stage.h", "coa_qstage.h", "coa_qmetrics.h", "coa_halved_dev.h", "coa_main_pick.h", "coa_engine.h",
            "coa_hostpool.h", "coa_job_bits.h", "coa_cert_scratch.h", "coa_lat_job.h", "coa_env.h", "coa_offsets.h", "coa_sums_tail.h", "coa_fe_pow29.h", "coa_ge_dec29.h", "coa_ge29.h",
-           "coa_batch_dev.h", "coa_resolve.h", "coa_resolve_ws.h", "coa_wire_parse.h", "coa_wire_dev.h", "coa_wire_mixed.h"]
+           "coa_batch_dev.h", "coa_resolve.h", "coa_resolve_ws.h", "coa_wire_parse.h", "coa_wire_dev.h", "coa_wire_layout.h"]
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffunction-sections", f"--offload-arch={ARCH}", "-I" + os.path.join(ROOT, "include")]
 
 

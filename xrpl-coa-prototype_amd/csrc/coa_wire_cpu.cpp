@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/coa_verify.h"
-#include "coa_wire_mixed.h"
+#include "coa_wire_layout.h"
 
 extern "C" int coa_cpu_wire_verdict_many(const uint8_t* frames, const uint64_t* frame_offsets, size_t n,
                                          uint64_t rng_seed, const uint8_t* committee_pks, const uint32_t* stakes,

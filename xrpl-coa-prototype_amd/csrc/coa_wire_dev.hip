@@ -138,7 +138,7 @@ __device__ __forceinline__ void scan_frame(const uint8_t* p, size_t len, uint32_
   }
 }
 
-__global__ void __launch_bounds__(64 * kWaves) k_wire_scan(const WireArgs a) {
+__global__ void __launch_bounds__(64 * kWaves) k_wire_scan(const WireHead a) {
   __shared__ __attribute__((aligned(16))) uint8_t stage[kWaves][kStage + 16];
   __shared__ uint8_t last[kWaves][COA_WIRE_DEV_MAX_ENTRIES];
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -182,13 +182,13 @@ struct SumsOne {
   }
   // Frame i's place: its exclusive sums `at`, its own contribution v.
   static __device__ __forceinline__ void place(const WireArgs& a, uint32_t i, const uint64_t at[3], const uint64_t v[3]) {
-    if (a.hoff) {
-      a.hoff[i] = at[0];
-      if (i == a.n - 1) a.hoff[a.n] = at[0] + v[0];
+    if (a.out.hoff) {
+      a.out.hoff[i] = at[0];
+      if (i == a.n - 1) a.out.hoff[a.n] = at[0] + v[0];
     }
-    if (a.voff) {
-      a.voff[i] = at[1];
-      if (i == a.n - 1) a.voff[a.n] = at[1] + v[1];
+    if (a.out.voff) {
+      a.out.voff[i] = at[1];
+      if (i == a.n - 1) a.out.voff[a.n] = at[1] + v[1];
     }
   }
 };
@@ -301,10 +301,9 @@ __global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_add(const typename
 }
 
 // A frame known to be a well-formed message of kind `want` into item `item` of
-// the arrays o (WireArgs: item i is frame i; a WireSet of the mixed mode: the
-// frame's slot).
-template <class O>
-__device__ __forceinline__ void decode_frame(const O& o, int32_t want, uint32_t item, const uint8_t* p, size_t len,
+// the arrays o (the index-aligned decode: item i is frame i; the mixed mode:
+// the frame's slot).
+__device__ __forceinline__ void decode_frame(const WireSet& o, int32_t want, uint32_t item, const uint8_t* p, size_t len,
                                              uint32_t lane, uint8_t* last) {
   CoaWpFrame f;
   (void)coa_wp_walk(p, len, &f);
@@ -347,21 +346,21 @@ __global__ void __launch_bounds__(64 * kWaves) k_wire_decode(const WireArgs a) {
   if (i >= a.n) return;
   if (a.kinds[i] != a.want) {
     // the placeholder: item i stays aligned with frame i and holds nothing
-    if (lane < 32) a.ids[(size_t)i * 32 + lane] = 0;
-    if (lane < 32) a.authors[(size_t)i * 32 + lane] = 0;
-    if (lane < 32 && a.vorigins) a.vorigins[(size_t)i * 32 + lane] = 0;
-    a.sigs[(size_t)i * 64 + lane] = 0;
-    if (lane == 0) a.rounds[i] = 0;
-    if (lane == 0 && a.pcounts) a.pcounts[i] = 0;
+    if (lane < 32) a.out.ids[(size_t)i * 32 + lane] = 0;
+    if (lane < 32) a.out.authors[(size_t)i * 32 + lane] = 0;
+    if (lane < 32 && a.out.vorigins) a.out.vorigins[(size_t)i * 32 + lane] = 0;
+    a.out.sigs[(size_t)i * 64 + lane] = 0;
+    if (lane == 0) a.out.rounds[i] = 0;
+    if (lane == 0 && a.out.pcounts) a.out.pcounts[i] = 0;
     return;
   }
   // the scan found the frame inside the buffer and well formed
   const uint64_t o0 = a.offs[i];
   const size_t len = (size_t)(a.offs[i + 1] - o0);
   if (len <= kStage)
-    decode_frame(a, a.want, i, stage_frame(a.frames + o0, (uint32_t)len, lane, stage[wave]), len, lane, last[wave]);
+    decode_frame(a.out, a.want, i, stage_frame(a.frames + o0, (uint32_t)len, lane, stage[wave]), len, lane, last[wave]);
   else
-    decode_frame(a, a.want, i, a.frames + o0, len, lane, last[wave]);
+    decode_frame(a.out, a.want, i, a.frames + o0, len, lane, last[wave]);
 }
 
 // The mixed mode: frame i of kind k into item slots[i] of kind k's arrays.  A
@@ -404,7 +403,7 @@ __global__ void __launch_bounds__(COA_WIRE_SCAN_BLOCK) k_wire_scatter(const int3
 
 }  // namespace
 
-hipError_t coa_launch_wire_scan(const WireArgs& a, hipStream_t s) {
+hipError_t coa_launch_wire_scan(const WireHead& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_wire_scan, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, a);
   return hipGetLastError();
@@ -424,15 +423,7 @@ hipError_t coa_launch_wire_decode(const WireArgs& a, hipStream_t s) {
 hipError_t coa_launch_wire_decode_mixed(const WireMixedArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   const uint32_t blocks = (a.n + COA_WIRE_SCAN_BLOCK - 1) / COA_WIRE_SCAN_BLOCK;
-  WireArgs scan{};  // k_wire_scan as it is: kinds, hb and nv of every frame
-  scan.frames = a.frames;
-  scan.offs = a.offs;
-  scan.frame_bytes = a.frame_bytes;
-  scan.n = a.n;
-  scan.kinds = a.kinds;
-  scan.hb = a.hb;
-  scan.nv = a.nv;
-  hipLaunchKernelGGL(k_wire_scan, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, scan);
+  hipLaunchKernelGGL(k_wire_scan, dim3((a.n + kWaves - 1) / kWaves), dim3(64 * kWaves), 0, s, a);
   hipLaunchKernelGGL(k_wire_block_totals<SumsMixed>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
   hipLaunchKernelGGL(k_wire_scan_totals<SumsMixed>, dim3(1), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a, blocks);
   hipLaunchKernelGGL(k_wire_add<SumsMixed>, dim3(blocks), dim3(COA_WIRE_SCAN_BLOCK), 0, s, a);
